@@ -14,6 +14,11 @@
 # after the reference's row-group pruning — the same rows the reference scan
 # would decode). Weak scaling: each rank owns its own shard (BASELINE
 # config 4: SSTs sharded per GPU, disjoint series spaces via per-rank seed).
+#
+# A plain run does only the headline: set up, warm up, time --steps steps,
+# print the result line (roofline/cpu_baseline null). --full adds the
+# roofline kernel pass, the cpu_baseline legs and the [bench-extra] lines.
+# --dump-outputs DIR writes the last timed step's result table as .npy.
 import argparse
 import json
 import os
@@ -174,6 +179,47 @@ def merge_bucket_partials(series_t, bucket_t, sum_t, cnt_t):
     return out_s, out_b, out_v, out_c
 
 
+DUMP_BUDGET_BYTES = 48 * 2**20  # headroom under the 64 MB ceiling
+
+
+def dump_outputs(out_dir, res, seed):
+    """--dump-outputs: write the result table of the last timed step as
+    out_dir/<column>.npy, float64 each. u64 series ids do not fit a float64,
+    so they go out as two exact halves (series_id_hi/_lo, 32 bits each).
+    Tables larger than the 64 MB budget are cut to a seeded row sample
+    (ascending row indices, also written as rows.npy); n_groups.npy holds
+    the full table's group count either way."""
+    os.makedirs(out_dir, exist_ok=True)
+    if isinstance(res, dict):  # config 5: merged tensors after the all-gather
+        cols = {k: v.cpu().numpy() for k, v in res["merged"].items()}
+        cols["series_id"] = cols["series_id"].view(np.uint64)
+        n = len(cols["series_id"])
+        take = lambda idx: {k: (v if idx is None else v[idx])  # noqa: E731
+                            for k, v in cols.items()}
+        n_files = len(cols) + 3
+    else:
+        n = res.n_groups
+        take = res.take
+        n_files = len(res.take(np.zeros(0, np.int64))) + 3
+    k = DUMP_BUDGET_BYTES // (8 * n_files)
+    idx = None
+    if n > k:
+        idx = np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+    out = take(idx)
+    sid = out.pop("series_id").astype(np.uint64, copy=False)
+    out["series_id_hi"] = sid >> np.uint64(32)
+    out["series_id_lo"] = sid & np.uint64(0xFFFFFFFF)
+    out["rows"] = np.arange(n) if idx is None else idx
+    out["n_groups"] = np.array([n])
+    total = 0
+    for name, a in out.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+    log(f"dumped {len(out)} arrays ({len(out['rows'])} of {n} groups, "
+        f"{total / 2**20:.1f} MB) to {out_dir}")
+
+
 def run_extras(args, device, opmap):
     """Labeled non-headline workload lines (driver-visible via stderr):
     the uncompressed config-2 variant, config 3 (series-set predicate +
@@ -301,6 +347,16 @@ def main():
     p.add_argument("--no-extras", action="store_true",
                    help="skip the extra labeled workload lines "
                         "(uncompressed variant, config 3, ts-overlap)")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline run also measure everything "
+                        "else: the roofline kernel pass, the cpu_baseline "
+                        "legs and the extra labeled workload lines. Off by "
+                        "default: a plain run sets up, warms up, times "
+                        "--steps steps and prints the result line.")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the result table of the LAST timed step as "
+                        "DIR/<column>.npy (float64; a fixed seeded row "
+                        "sample when the table exceeds 64 MB)")
     args = p.parse_args()
 
     rank = int(os.environ.get("RANK", 0))
@@ -417,9 +473,10 @@ def main():
         except OSError:
             pass
 
-    def step(copy=False, prep=prep):
+    def step(copy=False, prep=prep, hold=False):
         if not (args.config5 and dist):
-            return prep.exec_agg(ops=ops, bucket_ms=args.bucket_ms, copy=copy)
+            return prep.exec_agg(ops=ops, bucket_ms=args.bucket_ms, copy=copy,
+                                 hold=hold)
         # config 5: local bucket partials -> all-gather over RCCL (xGMI) ->
         # combine on the GPU; part of the timed step
         res = prep.exec_agg(ops=ops | 2, bucket_ms=args.bucket_ms, copy=True)
@@ -449,7 +506,10 @@ def main():
         ms, mb, mv, mc = merge_bucket_partials(ss, bb, vv, cc)
         if backend == "nccl":
             torch.cuda.synchronize(device)
-        return {"n_groups": int(ms.numel()), "merged_count": int(mc.sum().item())}
+        return {"n_groups": int(ms.numel()),
+                "merged_count": int(mc.sum().item()),
+                "merged": {"series_id": ms, "bucket": mb, "sum": mv,
+                           "count": mc}}
 
     # warmup (one materialized run for the group count, the rest light);
     # touch every pipeline slot so all tables/scratch are allocated untimed
@@ -471,9 +531,14 @@ def main():
     torch.cuda.synchronize(device)
     t_start = time.time()
     agg_kernel_ms = []
+    # --dump-outputs: the LAST timed step keeps its result table in the
+    # library's host buffer (no extra copy inside the timed region); it is
+    # copied out and released after the clock stops.
+    dump = args.dump_outputs is not None
+    last_res = None
     if n_pipe == 1:
-        for _ in range(args.steps):
-            step()
+        for i in range(args.steps):
+            last_res = step(hold=dump and i == args.steps - 1)
             agg_kernel_ms.append(prep.stats()["agg_kernel_ms"])
     else:
         # concurrent scans: ctypes releases the GIL inside hx_exec_agg,
@@ -487,16 +552,21 @@ def main():
         def timed_step(i):
             p_ = preps[i % n_pipe]
             with locks[i % n_pipe]:
-                step(prep=p_)
-                return p_.stats()["agg_kernel_ms"]
+                r = step(prep=p_, hold=dump and i == args.steps - 1)
+                return p_.stats()["agg_kernel_ms"], r
 
         with ThreadPoolExecutor(max_workers=n_pipe) as ex:
-            for k in ex.map(timed_step, range(args.steps)):
+            for k, last_res in ex.map(timed_step, range(args.steps)):
                 agg_kernel_ms.append(k)
     torch.cuda.synchronize(device)
     if dist:
         dist.barrier()
     elapsed = time.time() - t_start
+
+    if dump and rank == 0:
+        dump_outputs(args.dump_outputs, last_res, args.seed)
+    if hasattr(last_res, "close"):
+        last_res.close()
 
     # max over ranks of elapsed; sum over ranks of rows
     rows_scanned = prep.stats()["rows_scanned"]
@@ -530,42 +600,46 @@ def main():
         # traffic = PMC-measured HBM bytes per launch for THIS workload
         # label (rocprofv3 --pmc, profiles/roofline_traffic.json), or via
         # HX_ROOFLINE_TRAFFIC; null when unmeasured.
-        my_rows = prep.stats()["rows_scanned"]
-        if n_pipe > 1 and not (args.config5 and dist):
-            solo = []
-            for _ in range(3):
-                step(prep=preps[0])
-                solo.append(preps[0].stats()["agg_kernel_ms"])
-            k_ms = float(np.mean(solo))
-            k_basis = "solo pipeline-1 pass (HIP events, engine stream)"
-        else:
-            k_ms = float(np.mean(agg_kernel_ms))
-            k_basis = "timed-region kernel HIP events (pipeline 1)"
-        algo_bytes = my_rows * 24.0
-        achieved = algo_bytes / (k_ms * 1e-3)
-        peak = 8.0e12
-        traffic_env = os.environ.get("HX_ROOFLINE_TRAFFIC")
-        if not traffic_env:
-            tj = os.path.join(REPO, "profiles", "roofline_traffic.json")
-            if os.path.exists(tj):
-                with open(tj) as f:
-                    tdata = json.load(f).get(workload)
-                if tdata and tdata.get("traffic_bytes_per_scanned_row"):
-                    traffic_env = str(tdata["traffic_bytes_per_scanned_row"] *
-                                      my_rows)
-        roofline = {
-            "bound": "hbm",
-            "achieved": achieved / 1e9,
-            "peak": peak / 1e9,
-            "unit": "GB/s",
-            "frac": achieved / peak,
-            "traffic": float(traffic_env) if traffic_env else None,
-            "kernel_ms": k_ms,
-            "basis": k_basis,
-        }
+        # Measured under --full only (the solo pass is a run of its own);
+        # a plain run reports roofline: null.
+        roofline = None
+        if args.full:
+            my_rows = prep.stats()["rows_scanned"]
+            if n_pipe > 1 and not (args.config5 and dist):
+                solo = []
+                for _ in range(3):
+                    step(prep=preps[0])
+                    solo.append(preps[0].stats()["agg_kernel_ms"])
+                k_ms = float(np.mean(solo))
+                k_basis = "solo pipeline-1 pass (HIP events, engine stream)"
+            else:
+                k_ms = float(np.mean(agg_kernel_ms))
+                k_basis = "timed-region kernel HIP events (pipeline 1)"
+            algo_bytes = my_rows * 24.0
+            achieved = algo_bytes / (k_ms * 1e-3)
+            peak = 8.0e12
+            traffic_env = os.environ.get("HX_ROOFLINE_TRAFFIC")
+            if not traffic_env:
+                tj = os.path.join(REPO, "profiles", "roofline_traffic.json")
+                if os.path.exists(tj):
+                    with open(tj) as f:
+                        tdata = json.load(f).get(workload)
+                    if tdata and tdata.get("traffic_bytes_per_scanned_row"):
+                        traffic_env = str(
+                            tdata["traffic_bytes_per_scanned_row"] * my_rows)
+            roofline = {
+                "bound": "hbm",
+                "achieved": achieved / 1e9,
+                "peak": peak / 1e9,
+                "unit": "GB/s",
+                "frac": achieved / peak,
+                "traffic": float(traffic_env) if traffic_env else None,
+                "kernel_ms": k_ms,
+                "basis": k_basis,
+            }
 
         cpu = None
-        if not args.no_cpu_baseline and n_gpus == 1:
+        if args.full and not args.no_cpu_baseline and n_gpus == 1:
             ncores = args.cpu_cores if args.cpu_cores > 0 \
                 else (os.cpu_count() or 1)
             log(f"running cpu_baseline (native C++ leg, {ncores} threads)...")
@@ -590,8 +664,9 @@ def main():
             else:
                 cpu = oracle_leg
 
-        if not args.no_extras and world <= 1 and not args.config5 \
-                and args.selectivity == 0 and not args.bucket_ms:
+        if args.full and not args.no_extras and world <= 1 \
+                and not args.config5 and args.selectivity == 0 \
+                and not args.bucket_ms:
             run_extras(args, device, opmap)
 
         result = {

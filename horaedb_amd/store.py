@@ -134,6 +134,51 @@ def _np(ptr, n, dtype):
     return np.ctypeslib.as_array(ptr, shape=(n,)).astype(dtype, copy=True)
 
 
+class HeldResult:
+    """An exec_agg result still held in the library's host buffer (the
+    hx_result_table the C caller receives). take() copies rows out as numpy
+    arrays; close() hands the buffer back (hx_result_free)."""
+
+    def __init__(self, out, ops, bucket_ms):
+        self._out = out
+        self._ops = ops
+        self._bucket_ms = bucket_ms
+        self.n_groups = out.contents.n_groups
+
+    def take(self, idx=None):
+        """The result columns as numpy copies: every group (idx=None) or
+        the rows of the index array idx."""
+        t = self._out.contents
+        n = self.n_groups
+        ops = self._ops
+
+        def col(ptr, dtype):
+            if idx is None or not ptr or n == 0:
+                return _np(ptr, n, dtype)
+            return np.ctypeslib.as_array(ptr, shape=(n,))[idx].astype(
+                dtype, copy=False)
+
+        res = {"series_id": col(t.series_id, np.uint64)}
+        if self._bucket_ms:
+            res["bucket"] = col(t.bucket, np.int64)
+        if ops & AGG_SUM:
+            res["sum"] = col(t.sum, np.float64)
+        if ops & AGG_COUNT:
+            res["count"] = col(t.count, np.uint64)
+        if ops & AGG_MIN:
+            res["vmin"] = col(t.vmin, np.float64)
+        if ops & AGG_MAX:
+            res["vmax"] = col(t.vmax, np.float64)
+        if ops & AGG_AVG:
+            res["avg"] = col(t.avg, np.float64)
+        return res
+
+    def close(self):
+        if self._out is not None:
+            _lib.hx_result_free(self._out)
+            self._out = None
+
+
 class Prepared:
     """A staged scan (column chunks resident in HBM). exec_agg is the timed
     hot path."""
@@ -142,32 +187,22 @@ class Prepared:
         self._store = store
         self._h = handle
 
-    def exec_agg(self, ops=AGG_SUM | AGG_COUNT, bucket_ms=0, copy=True):
+    def exec_agg(self, ops=AGG_SUM | AGG_COUNT, bucket_ms=0, copy=True,
+                 hold=False):
         """copy=False: run the full query (result lands in host memory) but
-        skip the numpy materialization — for benchmarking loops."""
+        skip the numpy materialization — for benchmarking loops.
+        hold=True: same run, but return the result still in the library's
+        buffer as a HeldResult (the caller copies out later and closes it)."""
         spec = _AggSpec(ops=ops, bucket_ms=bucket_ms)
         out = C.POINTER(_ResultTable)()
         _check(_lib.hx_exec_agg(self._h, C.byref(spec), C.byref(out)))
-        t = out.contents
-        n = t.n_groups
-        if not copy:
-            _lib.hx_result_free(out)
-            return {"n_groups": n}
-        res = {"series_id": _np(t.series_id, n, np.uint64)}
-        if bucket_ms:
-            res["bucket"] = _np(t.bucket, n, np.int64)
-        if ops & AGG_SUM:
-            res["sum"] = _np(t.sum, n, np.float64)
-        if ops & AGG_COUNT:
-            res["count"] = _np(t.count, n, np.uint64)
-        if ops & AGG_MIN:
-            res["vmin"] = _np(t.vmin, n, np.float64)
-        if ops & AGG_MAX:
-            res["vmax"] = _np(t.vmax, n, np.float64)
-        if ops & AGG_AVG:
-            res["avg"] = _np(t.avg, n, np.float64)
-        _lib.hx_result_free(out)
-        return res
+        held = HeldResult(out, ops, bucket_ms)
+        if hold:
+            return held
+        try:
+            return held.take() if copy else {"n_groups": held.n_groups}
+        finally:
+            held.close()
 
     def stats(self):
         st = _ExecStats()

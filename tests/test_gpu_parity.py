@@ -85,6 +85,35 @@ def test_middle_range_all_ops(ds_plain):
     check_parity(out, middle_range(m), ops=OPS_ALL)
 
 
+def test_held_result_matches_copied_result(ds_plain):
+    # exec_agg(hold=True) keeps the table in the library's buffer; take()
+    # (whole, then an index subset) must return what copy=True returns.
+    # min/max/count are order-independent => bit-exact; f64 sums re-run the
+    # atomics in another order => the suite's 1e-9 relative bar.
+    out, m = ds_plain
+    from horaedb_amd import Store
+    with Store(out) as st, st.prepare(middle_range(m), devices=[0]) as pr:
+        exp = pr.exec_agg(ops=OPS_ALL, bucket_ms=60_000)
+        held = pr.exec_agg(ops=OPS_ALL, bucket_ms=60_000, hold=True)
+        try:
+            assert held.n_groups == len(exp["series_id"]) > 4
+            whole = held.take()
+            idx = np.array([0, 3, held.n_groups - 1])
+            part = held.take(idx)
+        finally:
+            held.close()
+        held.close()  # idempotent
+    assert set(whole) == set(part) == set(exp)
+    for k in exp:
+        assert whole[k].dtype == part[k].dtype == exp[k].dtype
+        if k in ("sum", "avg"):
+            np.testing.assert_allclose(whole[k], exp[k], rtol=1e-9)
+            np.testing.assert_allclose(part[k], exp[k][idx], rtol=1e-9)
+        else:
+            np.testing.assert_array_equal(whole[k], exp[k])
+            np.testing.assert_array_equal(part[k], exp[k][idx])
+
+
 def test_narrow_range_crossing_row_groups(ds_plain):
     out, m = ds_plain
     lo = m["ts_start"] + 37 * m["step_ms"]

@@ -45,7 +45,7 @@ timeout 900 rocprofv3 --kernel-trace --stats -d "$OUT/ktrace2" -o ktrace2 \
 
 # full driver-like run last (snappy headline, pipeline 3, extras, baselines)
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
-timeout 1200 python bench.py --steps 10 --warmup 3 \
+timeout 1200 python bench.py --steps 10 --warmup 3 --full \
     > gpurun_out/r02b_full.json 2> gpurun_out/r02b_full.log
 echo "full rc=$?"
 tail -3 gpurun_out/r02b_full.log

@@ -25,7 +25,7 @@ run def_pipe3    ""            "--compression none --pipeline 3"
 run snappy_def   ""            ""
 
 # full driver-like run with extras + cpu baselines (native leg fix check)
-timeout 1200 python bench.py --steps 8 --warmup 2 \
+timeout 1200 python bench.py --steps 8 --warmup 2 --full \
     > gpurun_out/r02e_full.json 2> gpurun_out/r02e_full.log
 echo "full rc=$?"
 grep -E "bench-extra|native|index query" gpurun_out/r02e_full.log | tail -8

@@ -11,7 +11,7 @@ echo "pytest rc=$?"; tail -2 gpurun_out/r02m_pytest.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/r02m_smoke.log 2>&1
 echo "smoke rc=$?"; tail -1 gpurun_out/r02m_smoke.log
 
-timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 \
+timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 --full \
     > gpurun_out/r02m_bench.json 2> gpurun_out/r02m_bench.log
 echo "bench rc=$?"
 tail -1 gpurun_out/r02m_bench.json | head -c 600; echo
