@@ -28,6 +28,7 @@
 
 #include "hx_kernels.h"
 #include "hx_internal.h"
+#include "snappy_stored.h"
 
 // ---------------------------------------------------------------------------
 // Zstd page codec (config.rs:84 includes Zstd): decompressed on the HOST at
@@ -357,6 +358,9 @@ struct DevPlan {
     size_t blob_bytes = 0;
     size_t dec_bytes = 0;
     int64_t rows_scanned = 0;
+    // stored Snappy pages read in place from the blob (hx_get_decode_stats)
+    uint64_t pages_in_place = 0;
+    uint64_t bytes_in_place = 0;
 
     // host staging
     uint8_t* h_blob = nullptr;
@@ -551,6 +555,9 @@ static hx_status stage_device(hx_prepared* P, DevPlan& plan,
                 size_t reserve = size_t(cr.comp_size);
                 if (cr.codec == hx::CODEC_ZSTD)
                     reserve = std::max(reserve, size_t(cr.uncomp_size));
+                // Snappy chunks: room to shift a stored-literal page so its
+                // body lands 64-byte aligned (pad <= 63, see the page walk)
+                if (cr.codec == hx::CODEC_SNAPPY) reserve += 64;
                 blob_off = align64(blob_off + reserve);
                 jobs.push_back(j);
             }
@@ -691,10 +698,38 @@ static hx_status stage_device(hx_prepared* P, DevPlan& plan,
                     break;
                 }
                 raw_size = want;
-            } else {
-                std::memcpy(plan.h_blob + j.dst_off, src, payload);
             }
-            if (j.codec == hx::CODEC_SNAPPY && dp->is_compressed) {
+            // Stored Snappy page (preamble + ONE literal covering the whole
+            // page — what the writer emits for incompressible data): nothing
+            // to decode. The payload goes into the blob verbatim, shifted by
+            // pad so the literal body sits on a 64-byte boundary, and the
+            // column offset points at the body: the scan kernels read it in
+            // place like an uncompressed PLAIN page (no SnappyPageDesc, no
+            // dec space). PLAIN 8-byte columns only; dictionary/DELTA pages
+            // and byte-value stores keep the decoder path.
+            bool stored = false;
+            if (j.codec == hx::CODEC_SNAPPY && dp->is_compressed &&
+                dp->encoding == hx::ENC_PLAIN && !(bytes_val && j.col == 2) &&
+                dp->uncompressed_size >= dp->def_level_bytes) {
+                const uint32_t ulen =
+                    (uint32_t)(size_t(dp->uncompressed_size) -
+                               size_t(dp->def_level_bytes));
+                uint32_t body_off = 0;
+                if (hx_snappy_stored_literal(src, payload, ulen, &body_off)) {
+                    const size_t pad = (64 - (body_off & 63u)) & 63u;
+                    // reserve = comp_size + 64 >= pad + payload
+                    std::memcpy(plan.h_blob + j.dst_off + pad, src, payload);
+                    data_off = j.dst_off + pad + body_off;
+                    raw_size = ulen;
+                    stored = true;
+                    std::lock_guard<std::mutex> g(mu);
+                    plan.pages_in_place++;
+                    plan.bytes_in_place += ulen;
+                }
+            }
+            if (!stored && !(j.codec == hx::CODEC_ZSTD && dp->is_compressed))
+                std::memcpy(plan.h_blob + j.dst_off, src, payload);
+            if (!stored && j.codec == hx::CODEC_SNAPPY && dp->is_compressed) {
                 std::lock_guard<std::mutex> g(mu);
                 hx::SnappyPageDesc sp{};
                 sp.src_off = j.dst_off;
@@ -2079,6 +2114,81 @@ extern "C" void hx_result_free(hx_result_table* t) {
 extern "C" hx_status hx_get_stats(hx_prepared* P, hx_exec_stats* out) {
     if (!P || !out) return fail(HX_ERR_INVALID, "null argument");
     *out = P->last_stats;
+    return HX_OK;
+}
+
+extern "C" hx_status hx_get_decode_stats(hx_prepared* P, hx_decode_stats* out) {
+    if (!P || !out) return fail(HX_ERR_INVALID, "null argument");
+    hx_decode_stats s{};
+    for (const DevPlan& plan : P->plans) {
+        s.pages_in_place += plan.pages_in_place;
+        s.bytes_in_place += plan.bytes_in_place;
+        s.pages_decoded += plan.snappy_pages.size();
+        for (const auto& sp : plan.snappy_pages)
+            s.bytes_decoded_out += sp.uncomp_len;
+    }
+    *out = s;
+    return HX_OK;
+}
+
+extern "C" hx_status hx_debug_snappy_decompress(
+    const uint8_t* streams, const uint64_t* offs, const uint32_t* comp_lens,
+    const uint32_t* uncomp_lens, uint32_t n, uint8_t* out,
+    const uint64_t* out_offs, uint64_t* n_errors) {
+    if (!n_errors || (n && (!streams || !offs || !comp_lens || !uncomp_lens ||
+                            !out || !out_offs)))
+        return fail(HX_ERR_INVALID, "null argument");
+    *n_errors = 0;
+    if (n == 0) return HX_OK;
+    // same layout staging produces: payloads 64-byte aligned in one blob,
+    // outputs 64-byte aligned in one dec region, 64 bytes of slack on each
+    std::vector<hx::SnappyPageDesc> pages(n);
+    size_t blob_bytes = 0, dec_bytes = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        pages[i].src_off = blob_bytes;
+        pages[i].dst_off = hx::OFF_DEC | dec_bytes;
+        pages[i].comp_len = comp_lens[i];
+        pages[i].uncomp_len = uncomp_lens[i];
+        blob_bytes = align64(blob_bytes + comp_lens[i]);
+        dec_bytes = align64(dec_bytes + uncomp_lens[i]);
+    }
+    std::vector<uint8_t> h_blob(blob_bytes + 64, 0);
+    for (uint32_t i = 0; i < n; i++)
+        std::memcpy(h_blob.data() + pages[i].src_off, streams + offs[i],
+                    comp_lens[i]);
+    struct DevBufs {
+        void* p[4] = {nullptr, nullptr, nullptr, nullptr};
+        ~DevBufs() {
+            for (void* q : p)
+                if (q) hipFree(q);
+        }
+    } dev;
+    HIP_TRY(hipMalloc(&dev.p[0], h_blob.size()));
+    HIP_TRY(hipMalloc(&dev.p[1], dec_bytes + 64));
+    HIP_TRY(hipMalloc(&dev.p[2], size_t(n) * sizeof(hx::SnappyPageDesc)));
+    HIP_TRY(hipMalloc(&dev.p[3], sizeof(unsigned long long)));
+    HIP_TRY(hipMemcpy(dev.p[0], h_blob.data(), h_blob.size(),
+                      hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(dev.p[1], 0xEE, dec_bytes + 64));
+    HIP_TRY(hipMemcpy(dev.p[2], pages.data(),
+                      size_t(n) * sizeof(hx::SnappyPageDesc),
+                      hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(dev.p[3], 0, sizeof(unsigned long long)));
+    HIP_TRY(hx::launch_snappy(nullptr, (const uint8_t*)dev.p[0],
+                              (uint8_t*)dev.p[1],
+                              (const hx::SnappyPageDesc*)dev.p[2], n,
+                              (unsigned long long*)dev.p[3]));
+    HIP_TRY(hipDeviceSynchronize());
+    std::vector<uint8_t> h_dec(dec_bytes + 64);
+    HIP_TRY(hipMemcpy(h_dec.data(), dev.p[1], h_dec.size(),
+                      hipMemcpyDeviceToHost));
+    unsigned long long errs = 0;
+    HIP_TRY(hipMemcpy(&errs, dev.p[3], sizeof(errs), hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < n; i++)
+        std::memcpy(out + out_offs[i],
+                    h_dec.data() + (pages[i].dst_off & hx::OFF_MASK),
+                    uncomp_lens[i]);
+    *n_errors = errs;
     return HX_OK;
 }
 

@@ -13,3 +13,15 @@ hx_status set_error(hx_status code, const std::string& msg);
 const std::string& store_path(hx_handle* h);
 
 }  // namespace hx_int
+
+// Test hook (exported, not part of the public C-ABI): run the production
+// Snappy decode launch once over n caller-built streams on the current
+// device. Stream i is streams[offs[i], offs[i] + comp_lens[i]); it is
+// uploaded 64-byte aligned (as staging places page payloads) and decoded
+// into uncomp_lens[i] bytes, which are copied back to out + out_offs[i].
+// *n_errors receives the decoder's error count (streams it rejected; their
+// output bytes are unspecified).
+extern "C" hx_status hx_debug_snappy_decompress(
+    const uint8_t* streams, const uint64_t* offs, const uint32_t* comp_lens,
+    const uint32_t* uncomp_lens, uint32_t n, uint8_t* out,
+    const uint64_t* out_offs, uint64_t* n_errors);

@@ -2119,7 +2119,23 @@ __device__ __forceinline__ uint32_t snappy_varint(const uint8_t* p,
 //   2. 4 KB LDS output ring per wave (16 KB per 256-thread block => full
 //      32-wave occupancy), flushed to HBM in coalesced spans; matches read
 //      the ring, never global dst (no vmcnt round trips).
+//   3. DIRECT runs: where a run's output is a function of a few registers
+//      it is stored straight to dst, 16 B per lane, and never round-trips
+//      through the ring: pair runs ([x, x] per pair, taken when d is
+//      8-aligned) and fused same-offset runs with off in {1,2,4,8,16} of at
+//      least SNAP_DIRECT_MIN bytes (one 16-byte pattern, any d: the ragged
+//      ends up to the 16-aligned middle go out as bytes). Huge literals
+//      copy src -> dst the same way.
+// RING INVARIANT, which every direct path restores before the element loop
+// continues: flushed == d; the ring holds the valid output bytes of
+// [max(0, d - SNAP_RING), d) (direct paths mirror their last SNAP_RING bytes
+// with wide LDS stores); tail0/tail1/pend are reloaded from the ring
+// (rwin_reload). Back-references up to SNAP_RING / 2 read the ring, longer
+// ones the drained global path. No path reads past comp_len or writes past
+// uncomp_len; a malformed stream bumps err_flag.
 #define SNAP_RING 4096u
+// fused same-offset runs at least this long bypass the ring (direct stores)
+#define SNAP_DIRECT_MIN 256u
 
 struct SnapStream {
     const uint64_t* words;   // aligned view of the page payload
@@ -2158,14 +2174,26 @@ struct SnapStream {
     }
 };
 
-// flush ring bytes [f, f+len) to dst (coalesced u32 stores when everything
-// is 4-aligned, else bytes). Ring spans wrap at SNAP_RING.
+// flush ring bytes [f, f+len) to dst: 16 B per lane while the ring offset
+// and the dst offset are both 16-aligned (dst itself is 64-aligned), then
+// coalesced u32 stores when everything left is 4-aligned, else bytes. Ring
+// spans wrap at SNAP_RING.
 __device__ __forceinline__ void snap_flush(uint8_t* __restrict__ dst,
                                            const uint8_t* ring, uint32_t f,
                                            uint32_t len, uint32_t lane) {
     while (len) {
-        const uint32_t r0 = f & (SNAP_RING - 1);
-        const uint32_t span = min(len, SNAP_RING - r0);
+        uint32_t r0 = f & (SNAP_RING - 1);
+        uint32_t span = min(len, SNAP_RING - r0);
+        len -= span;
+        if (((r0 | f) & 15u) == 0 && span >= 16u) {
+            const uint32_t n16 = span >> 4;
+            for (uint32_t i = lane; i < n16; i += 64)
+                *(ulonglong2*)(dst + f + 16 * i) =
+                    *(const ulonglong2*)(ring + r0 + 16 * i);
+            r0 += n16 << 4;
+            f += n16 << 4;
+            span -= n16 << 4;
+        }
         if ((r0 & 3u) == 0 && (f & 3u) == 0 && (span & 3u) == 0) {
             const uint32_t words = span >> 2;
             for (uint32_t i = lane; i < words; i += 64) {
@@ -2178,8 +2206,34 @@ __device__ __forceinline__ void snap_flush(uint8_t* __restrict__ dst,
                 dst[f + i] = ring[r0 + i];
         }
         f += span;
-        len -= span;
     }
+}
+
+// Byte a (0..15) of a 16-byte pattern held as two LE u64 halves.
+__device__ __forceinline__ uint8_t snap_qbyte(uint64_t q0, uint64_t q1,
+                                              uint32_t a) {
+    return (uint8_t)(((a & 8u) ? q1 : q0) >> (8u * (a & 7u)));
+}
+
+// Write output bytes [A, B) of a 16-periodic run, out[a] = Q[a & 15], to
+// `base` (dst, or the ring with MASK = SNAP_RING - 1): bytes up to the
+// first 16-aligned position, 16 B per lane over the aligned middle, bytes
+// after it. Correct for any A, B; base + (a & MASK) is 16-aligned whenever
+// a is.
+template <uint32_t MASK>
+__device__ __forceinline__ void snap_emit_q(uint8_t* base, uint32_t A,
+                                            uint32_t B, uint64_t q0,
+                                            uint64_t q1, uint32_t lane) {
+    uint32_t A16 = (A + 15u) & ~15u;
+    uint32_t B16 = B & ~15u;
+    if (A16 >= B16) A16 = B16 = B;   // no aligned middle: all bytes
+    for (uint32_t a = A + lane; a < A16; a += 64)
+        base[a & MASK] = snap_qbyte(q0, q1, a & 15u);
+    const ulonglong2 q = make_ulonglong2(q0, q1);
+    for (uint32_t a = A16 + 16u * lane; a < B16; a += 1024u)
+        *(ulonglong2*)(base + (a & MASK)) = q;
+    for (uint32_t a = B16 + lane; a < B; a += 64)
+        base[a & MASK] = snap_qbyte(q0, q1, a & 15u);
 }
 
 template <int MINW>
@@ -2187,7 +2241,7 @@ __global__ void __launch_bounds__(256, MINW)
 k_snappy_decompress(const uint8_t* __restrict__ blob, uint8_t* __restrict__ dec,
                     const SnappyPageDesc* __restrict__ pages, uint32_t n_pages,
                     unsigned long long* err_flag) {
-    __shared__ uint8_t ring_all[4][SNAP_RING];
+    __shared__ __attribute__((aligned(16))) uint8_t ring_all[4][SNAP_RING];
     const uint32_t lane = threadIdx.x & 63;
     uint8_t* const ring = ring_all[(threadIdx.x >> 6) & 3];
     const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -2294,22 +2348,65 @@ k_snappy_decompress(const uint8_t* __restrict__ blob, uint8_t* __restrict__ dec,
                 const uint8_t pbyte =
                     ring[(d - 1) & (SNAP_RING - 1)];
                 uint32_t consumed = 0;
+                // d 8-aligned (the data shape: an 8-byte literal, then 16
+                // bytes per pair): DIRECT mode — each lane builds its pair's
+                // 8 output bytes x in a register and stores [x, x] straight
+                // to dst (16 B per lane, 1 KB per wave iteration) and, with
+                // two 8-byte LDS stores, to the ring mirror; flushed tracks
+                // d, so no flush/room bookkeeping. Any other alignment keeps
+                // the ring path below.
+                const bool direct = (d & 7u) == 0;
                 for (;;) {
                     const uint32_t pp = pos + 10u * lane;
                     bool ok = pp + 10 <= clen &&
                               d + 16u * (lane + 1u) <= ulen;
-                    uint8_t b[7];
+                    // the pair's 10 bytes: one 8-byte and one 2-byte load
+                    // (in bounds: pp + 10 <= clen)
+                    uint64_t w = 0;
                     if (ok) {
-                        ok = src[pp] == 0x18u && src[pp + 8] == 0x15u &&
-                             src[pp + 9] == 0x08u;
-                        if (ok)
-                            for (int k = 0; k < 7; k++) b[k] = src[pp + 1 + k];
+                        uint16_t t2;
+                        __builtin_memcpy(&w, src + pp, 8);
+                        __builtin_memcpy(&t2, src + pp + 8, 2);
+                        ok = (w & 0xFFu) == 0x18u && t2 == 0x0815u;
                     }
                     const unsigned long long bm = __ballot(ok);
                     const uint32_t m =
                         (~bm == 0ull) ? 64u
                                       : (uint32_t)(__ffsll((long long)~bm) - 1);
                     if (m == 0) break;
+                    if (direct) {
+                        if (consumed == 0) {
+                            snap_flush(dst, ring, flushed, d - flushed, lane);
+                            flushed = d;
+                        }
+                        if (lane < m) {
+                            const uint64_t x =
+                                (w >> 8) | ((uint64_t)pbyte << 56);
+                            const uint32_t base = d + 16u * lane;
+                            if ((d & 15u) == 0) {
+                                *(ulonglong2*)(dst + base) =
+                                    make_ulonglong2(x, x);
+                            } else {
+                                // d = 8 mod 16: two 8-byte stores (rotating
+                                // 16 B chunks through the neighbour lane
+                                // measured no faster, profiles/README.md)
+                                *(uint64_t*)(dst + base) = x;
+                                *(uint64_t*)(dst + base + 8) = x;
+                            }
+                            *(uint64_t*)(ring + (base & (SNAP_RING - 1))) = x;
+                            *(uint64_t*)(ring +
+                                         ((base + 8) & (SNAP_RING - 1))) = x;
+                        }
+                        d += 16u * m;
+                        flushed = d;
+                        pos += 10u * m;
+                        consumed += m;
+                        if (m < 64u) break;
+                        continue;
+                    }
+                    uint8_t b[7];
+                    for (int k = 0; k < 7; k++)
+                        b[k] = (uint8_t)(w >> (8 * (k + 1)));
                     // ring room for 16*m bytes (+8 slop margin)
                     if (d + 16u * m + 8u > flushed + SNAP_RING) {
                         uint32_t want = d + 16u * m - (SNAP_RING / 2);
@@ -2363,15 +2460,24 @@ k_snappy_decompress(const uint8_t* __restrict__ blob, uint8_t* __restrict__ dec,
                     off = (uint32_t)((v >> 8) & 0xFFFFu);
                     hdr = 3;
                 }
-                if ((off == 1 || off == 2 || off == 4 || off == 8) &&
+                // head of a chain of identical long 2-byte-offset copies (a
+                // ts page is ~1000 of them): leave it to the fusing general
+                // path, whose direct run writes the whole chain at once
+                const bool chain =
+                    kind == 2 && len >= 32 &&
+                    (v & 0xFFFFFFull) == ((v >> 24) & 0xFFFFFFull) &&
+                    (v & 0xFFFFull) == ((v >> 48) & 0xFFFFull);
+                if (!chain &&
+                    (off == 1 || off == 2 || off == 4 || off == 8) &&
                     off <= d && pos + hdr <= clen && d + len <= ulen &&
                     d + len + 8 <= flushed + SNAP_RING) {
                     // pow2 period divides 8: the replicated pattern word is
                     // constant across every emitted 8-byte chunk
+                    // (doubling: 8*off -> 16*off -> ... -> 64 bits; off = 2
+                    // needs the << 32 step too)
                     uint64_t rep = tail0 >> (64 - 8 * off);
-                    if (off < 8) rep |= rep << (8 * off);
-                    if (off < 4) rep |= rep << 16;
-                    if (off < 2) rep |= rep << 32;
+                    for (uint32_t s = 8 * off; s < 64; s <<= 1)
+                        rep |= rep << s;
                     uint32_t rem = len;
                     while (rem >= 8) {
                         rwin_append(rep, 8);
@@ -2436,9 +2542,26 @@ k_snappy_decompress(const uint8_t* __restrict__ blob, uint8_t* __restrict__ dec,
                         for (uint32_t i = lane; i < len; i += 64)
                             dst[d + i] = src[pos + i];
                     }
-                    for (uint32_t i = lane; i < SNAP_RING; i += 64)
-                        ring[(d + len - SNAP_RING + i) & (SNAP_RING - 1)] =
-                            src[pos + len - SNAP_RING + i];
+                    // re-prime the ring with the literal's last SNAP_RING
+                    // bytes: 8 B per lane over the 8-aligned output
+                    // positions, bytes at the two ragged ends (source reads
+                    // stay inside the literal)
+                    {
+                        const uint32_t e = d + len;
+                        const uint32_t a_lo = e - SNAP_RING;   // >= d
+                        const uint32_t a8 = (a_lo + 7u) & ~7u;
+                        const uint32_t e8 = e & ~7u;
+                        // output position a <-> src[pos + (a - d)]
+                        for (uint32_t a = a_lo + lane; a < a8; a += 64)
+                            ring[a & (SNAP_RING - 1)] = src[pos + (a - d)];
+                        for (uint32_t a = a8 + 8u * lane; a < e8; a += 512u) {
+                            uint64_t x;
+                            __builtin_memcpy(&x, src + pos + (a - d), 8);
+                            *(uint64_t*)(ring + (a & (SNAP_RING - 1))) = x;
+                        }
+                        for (uint32_t a = e8 + lane; a < e; a += 64)
+                            ring[a & (SNAP_RING - 1)] = src[pos + (a - d)];
+                    }
                     d += len;
                     flushed = d;
                 } else {
@@ -2475,6 +2598,33 @@ k_snappy_decompress(const uint8_t* __restrict__ blob, uint8_t* __restrict__ dec,
                 // [d+L, d+L+len_k) from [d+L-off, ...) — the continuation
                 // of one periodic/shifted copy. The fused run executes as
                 // a single cooperative loop; per-tag cost = the parse.
+                // A ts page is ~1000 IDENTICAL 3-byte tags: count those 64
+                // at a time (lane k compares the tag at pos + 3k, ballot
+                // prefix) instead of parsing them one by one; the serial
+                // loop below picks up whatever differs.
+                if (kind == 2 && d + len <= ulen) {
+                    const uint32_t tag3 = (uint32_t)(v & 0xFFFFFFull);
+                    const uint32_t elen = len;
+                    for (;;) {
+                        const uint32_t pp = pos + 3u * lane;
+                        bool ok = pp + 3 <= clen;
+                        if (ok) {
+                            const uint32_t t = (uint32_t)src[pp] |
+                                               ((uint32_t)src[pp + 1] << 8) |
+                                               ((uint32_t)src[pp + 2] << 16);
+                            ok = t == tag3;
+                        }
+                        const unsigned long long bm = __ballot(ok);
+                        uint32_t m =
+                            (~bm == 0ull) ? 64u
+                                          : (uint32_t)(__ffsll((long long)~bm) - 1);
+                        m = min(m, (ulen - d - len) / elen);
+                        if (m == 0) break;
+                        len += m * elen;
+                        pos += 3u * m;
+                        if (m < 64u) break;
+                    }
+                }
                 for (;;) {
                     st.advance_to(pos);
                     const uint64_t nv = st.peek8(pos);
@@ -2500,7 +2650,54 @@ k_snappy_decompress(const uint8_t* __restrict__ blob, uint8_t* __restrict__ dec,
                     pos += nhdr;
                 }
                 if (d + len > ulen) { err = 1; break; }
-                if (off > SNAP_RING / 2) {
+                if (len >= SNAP_DIRECT_MIN &&
+                    (off == 1 || off == 2 || off == 4 || off == 8 ||
+                     off == 16)) {
+                    // DIRECT same-offset run: off divides 16, so every
+                    // 16-aligned output chunk of the run is the SAME 16
+                    // bytes Q, Q[a & 15] = out[a] = S[(a - d) mod off] with
+                    // S = the last off output bytes (register tail). Build
+                    // Q rotated for d's alignment, drain the ring, store the
+                    // run straight to dst 16 B per lane, and mirror its last
+                    // min(len, SNAP_RING) bytes into the ring the same way.
+                    uint64_t q0, q1;
+                    if (off <= 8) {
+                        // R[i] = out[d + i], period off | 8
+                        uint64_t rep = tail0 >> (64 - 8 * off);
+                        for (uint32_t s = 8 * off; s < 64; s <<= 1)
+                            rep |= rep << s;
+                        const uint32_t r = 8u * (d & 7u);
+                        q0 = r ? ((rep << r) | (rep >> (64 - r))) : rep;
+                        q1 = q0;
+                    } else {
+                        // T = out[d-16, d) = (tail1, tail0); Q = T rotated
+                        // left by d & 15 bytes
+                        uint64_t lo = tail1, hi = tail0;
+                        uint32_t r = d & 15u;
+                        if (r >= 8) {
+                            const uint64_t t = lo;
+                            lo = hi;
+                            hi = t;
+                            r -= 8;
+                        }
+                        if (r) {
+                            const uint32_t s = 8u * r;
+                            q0 = (lo << s) | (hi >> (64 - s));
+                            q1 = (hi << s) | (lo >> (64 - s));
+                        } else {
+                            q0 = lo;
+                            q1 = hi;
+                        }
+                    }
+                    snap_flush(dst, ring, flushed, d - flushed, lane);
+                    const uint32_t e = d + len;
+                    snap_emit_q<0xFFFFFFFFu>(dst, d, e, q0, q1, lane);
+                    snap_emit_q<SNAP_RING - 1>(
+                        ring, len >= SNAP_RING ? e - SNAP_RING : d, e, q0, q1,
+                        lane);
+                    d = e;
+                    flushed = e;
+                } else if (off > SNAP_RING / 2) {
                     // far back-reference (not produced for this data
                     // shape): flush + drain once, then chunked global
                     // reads of the (flushed, stable) pre-run bytes
@@ -2824,7 +3021,9 @@ hipError_t launch_snappy(hipStream_t s, const uint8_t* blob, uint8_t* dec,
     // HX_SNAPPY_MINW selects. Default 6 (24 waves/CU, 440 B scratch):
     // measured best in two same-box headline A/Bs (26.1 vs 27.0/27.1 ms
     // per step against MINW 1/5 at pipeline 3; 30.4 vs 31.0/31.3 solo) —
-    // the extra waves buy more than the spill costs.
+    // the extra waves buy more than the spill costs. Re-checked after the
+    // direct-run rewrite (576 B scratch at 6): 5/6/7 within run-to-run
+    // spread of each other, no value wins every pair — stays 6.
     int minw = 6;
     if (const char* e = getenv("HX_SNAPPY_MINW")) minw = atoi(e);
     if (minw >= 8)

@@ -74,6 +74,12 @@ class _ExecStats(C.Structure):
                 ("stage_ms", C.c_double)]
 
 
+class _DecodeStats(C.Structure):
+    _fields_ = [("pages_in_place", C.c_uint64), ("pages_decoded", C.c_uint64),
+                ("bytes_in_place", C.c_uint64),
+                ("bytes_decoded_out", C.c_uint64)]
+
+
 def _load():
     if not os.path.exists(_LIB):
         raise ImportError(
@@ -96,6 +102,7 @@ def _load():
                                 C.POINTER(_AggSpec), C.POINTER(_DeviceSet),
                                 C.POINTER(C.POINTER(_ResultTable))]
     lib.hx_get_stats.argtypes = [C.c_void_p, C.POINTER(_ExecStats)]
+    lib.hx_get_decode_stats.argtypes = [C.c_void_p, C.POINTER(_DecodeStats)]
     lib.hx_scan.argtypes = [C.c_void_p, C.POINTER(_ScanSpec),
                             C.POINTER(_DeviceSet), C.c_void_p, C.c_void_p]
     lib.hx_compact.argtypes = [C.c_void_p, _TimeRange, C.POINTER(_DeviceSet),
@@ -207,6 +214,13 @@ class Prepared:
     def stats(self):
         st = _ExecStats()
         _check(_lib.hx_get_stats(self._h, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in st._fields_}
+
+    def decode_stats(self):
+        """What staging did with the Snappy pages: stored (single-literal)
+        pages read in place vs pages the GPU decoder expands."""
+        st = _DecodeStats()
+        _check(_lib.hx_get_decode_stats(self._h, C.byref(st)))
         return {f: getattr(st, f) for f, _ in st._fields_}
 
     def close(self):

@@ -279,6 +279,19 @@ typedef struct {
 } hx_exec_stats;
 hx_status hx_get_stats(hx_prepared*, hx_exec_stats* out);
 
+/* What staging did with the prepared scan's Snappy data/dictionary pages
+ * (summed over devices). A "stored" page — length preamble plus one literal
+ * covering the whole page — is read in place from the staged blob; every
+ * other Snappy page goes through the GPU decoder on each decode pass. All
+ * zero for stores without Snappy pages. */
+typedef struct {
+    uint64_t pages_in_place;    /* stored pages read in place               */
+    uint64_t pages_decoded;     /* pages handed to the GPU Snappy decoder   */
+    uint64_t bytes_in_place;    /* uncompressed bytes of the in-place pages */
+    uint64_t bytes_decoded_out; /* bytes the decoder writes per decode pass */
+} hx_decode_stats;
+hx_status hx_get_decode_stats(hx_prepared*, hx_decode_stats* out);
+
 #ifdef __cplusplus
 }
 #endif
