@@ -381,17 +381,8 @@ struct DevPlan {
 
     // aggregate table (lazily sized)
     uint32_t slots = 0;
-    uint64_t* t_series = nullptr;
-    int64_t* t_bucket = nullptr;
-    uint32_t* t_state = nullptr;
-    double* t_sum = nullptr;
-    unsigned long long* t_cnt = nullptr;
-    unsigned long long* t_min = nullptr;
-    unsigned long long* t_max = nullptr;
-    uint8_t* t_slab = nullptr;      // AoS key-claim table
+    uint8_t* t_slab = nullptr;      // slot slab (key-claim or state-word)
     uint32_t slab_stride = 0;
-    uint8_t* t_rep = nullptr;       // per-XCD accumulator replicas (opt-in)
-    uint32_t rep_stride = 0;
     uint8_t* t_bstore = nullptr;    // direct-indexed bucket accumulators
     uint64_t bstore_cap = 0;
     unsigned long long* d_counters = nullptr;  // fill, overflow, matched, n_out
@@ -400,8 +391,6 @@ struct DevPlan {
     uint64_t sset_empty = ~0ull;
     uint32_t sset_mask = 0;
 
-    void* h_params = nullptr;   // pinned staging for kernel param structs
-    void* d_params = nullptr;
     bool decoded = false;       // delta/copy kernels already ran
     double decode_ms = 0;
 
@@ -411,7 +400,7 @@ struct DevPlan {
     void* d_sort_temp = nullptr;
     size_t sort_temp_cap = 0;
 
-    // series-range mode (k_scan_agg_range)
+    // series-range mode (k_scan_agg_range2)
     std::vector<int32_t> h_sst_rgs;     // rg indices grouped per SST, row order
     std::vector<int32_t> h_sst_rg_off;
     std::vector<int32_t> h_sst_rg_cnt;
@@ -919,10 +908,9 @@ static hx_status stage_device(hx_prepared* P, DevPlan& plan,
     // ---- slice + align row groups across SSTs ----------------------------
     // SSTs may carry different rows-per-series (time windows of 1 vs 2
     // points), so the k-th row group of two SSTs can cover very different
-    // series ranges. For the gang kernel's LDS table (and the group table's
-    // L2/L3 locality) the unit list is (a) split into ~half-row-group slices
-    // so one unit's distinct-series count stays under the LDS table size,
-    // and (b) ordered by FRACTIONAL row position within its SST — units at
+    // series ranges. For the group table's L2/L3 locality under the wave
+    // kernel the unit list is (a) split into ~half-row-group slices and
+    // (b) ordered by FRACTIONAL row position within its SST — units at
     // the same fraction cover the same series quantile of the shared series
     // universe. Speed-only: dispatch order is never relied on for
     // correctness; dedup successor links (next_rg) are remapped.
@@ -1240,19 +1228,13 @@ extern "C" void hx_prepared_free(hx_prepared* P) {
             if (plan.h_blob_pinned) hipHostFree(plan.h_blob);
             else free(plan.h_blob);
         }
-        if (plan.d_params) hipFree(plan.d_params);
-        if (plan.h_params) hipHostFree(plan.h_params);
         for (void* p : {(void*)plan.d_blob, (void*)plan.d_dec, (void*)plan.d_rgs,
                         (void*)plan.d_ssts, (void*)plan.d_clusters,
                         (void*)plan.d_members, (void*)plan.d_delta,
                         (void*)plan.d_ba,
                         (void*)plan.d_snappy, (void*)plan.d_rledict,
-                        (void*)plan.d_copies, (void*)plan.t_series,
-                        (void*)plan.t_bucket, (void*)plan.t_state,
-                        (void*)plan.t_sum, (void*)plan.t_cnt, (void*)plan.t_min,
-                        (void*)plan.t_max, (void*)plan.t_slab,
-                        (void*)plan.t_rep, (void*)plan.t_bstore,
-                        (void*)plan.d_counters,
+                        (void*)plan.d_copies, (void*)plan.t_slab,
+                        (void*)plan.t_bstore, (void*)plan.d_counters,
                         (void*)plan.d_sset, (void*)plan.d_sst_rgs,
                         (void*)plan.d_sst_rg_off, (void*)plan.d_sst_rg_cnt,
                         (void*)plan.d_range_bounds, (void*)plan.d_bound_rows})
@@ -1353,33 +1335,24 @@ uint32_t next_pow2_u32(uint64_t x) {
     return p;
 }
 
-hx_status alloc_table(DevPlan& plan, uint32_t slots, uint32_t ops, bool bucket,
+hx_status alloc_table(DevPlan& plan, uint32_t slots, uint32_t ops,
                       bool key_claim) {
-    (void)bucket;
-    // AoS slab strides: key-claim {key,sum,cnt[,min,max]} = 32/64;
+    // slab strides: key-claim {key,sum,cnt[,min,max]} = 32/64;
     // state mode {state,pad,series,bucket,sum,cnt[,min,max]} = 48/64
     uint32_t stride = key_claim
                           ? ((ops & (HX_AGG_MIN | HX_AGG_MAX)) ? 64u : 32u)
                           : ((ops & (HX_AGG_MIN | HX_AGG_MAX)) ? 64u : 48u);
-    const bool want_rep = key_claim && getenv("HX_XCD_REP") != nullptr;
-    if (plan.slots == slots && plan.t_slab && plan.slab_stride == stride &&
-        (plan.t_rep != nullptr) == want_rep)
+    if (plan.slots == slots && plan.t_slab && plan.slab_stride == stride)
         return HX_OK;
-    for (void** p : {(void**)&plan.t_series, (void**)&plan.t_bucket,
-                     (void**)&plan.t_state, (void**)&plan.t_sum,
-                     (void**)&plan.t_cnt, (void**)&plan.t_min,
-                     (void**)&plan.t_max, (void**)&plan.t_slab,
-                     (void**)&plan.t_rep})
-        if (*p) { hipFree(*p); *p = nullptr; }
+    if (plan.t_slab) { hipFree(plan.t_slab); plan.t_slab = nullptr; }
     plan.slots = slots;
     plan.slab_stride = stride;
     HIP_TRY(hipMalloc((void**)&plan.t_slab, size_t(slots) * stride));
-    if (key_claim && getenv("HX_XCD_REP")) {
-        plan.rep_stride = (ops & (HX_AGG_MIN | HX_AGG_MAX)) ? 32u : 16u;
-        HIP_TRY(hipMalloc((void**)&plan.t_rep,
-                          8ull * slots * plan.rep_stride));
-    }
     return HX_OK;
+}
+
+hx::AggTable agg_table(const DevPlan& plan) {
+    return hx::AggTable{plan.slots - 1, plan.t_slab, plan.slab_stride};
 }
 
 // ops mask for the kernel: AVG implies SUM+COUNT accumulation
@@ -1558,7 +1531,7 @@ static hx_status ensure_range(DevPlan& plan, const hx::AggParams& base) {
                       (size_t)(nb + 1) * n_ssts * 8));
     hx::RangeAux R{plan.d_range_bounds, plan.d_bound_rows, plan.d_sst_rgs,
                    plan.d_sst_rg_off,   plan.d_sst_rg_cnt, n_ssts,
-                   nb,                  2048,              0};
+                   nb,                  2048};
     ke = hx::launch_range_bounds(s, base, R, plan.d_bound_rows);
     if (ke != hipSuccess)
         return fail(HX_ERR_HIP, std::string("range bounds failed: ") +
@@ -1672,7 +1645,7 @@ hx_status exec_plan(hx_prepared* P, DevPlan& plan, const hx_agg_spec* agg,
 
     unsigned long long counters[6];
     for (int attempt = 0; attempt < 4; attempt++) {
-        hx_status st = alloc_table(plan, slots, ops, bucket, key_claim);
+        hx_status st = alloc_table(plan, slots, ops, key_claim);
         if (st != HX_OK) return st;
         if (n_buckets) {
             uint64_t need_b = (uint64_t)slots * n_buckets * bstride;
@@ -1689,12 +1662,8 @@ hx_status exec_plan(hx_prepared* P, DevPlan& plan, const hx_agg_spec* agg,
             HIP_TRY(hx::launch_init_slab(s, plan.t_slab, slots,
                                          plan.slab_stride));
             if (n_buckets)
-                HIP_TRY(hx::launch_init_rep(
+                HIP_TRY(hx::launch_init_accum_rows(
                     s, plan.t_bstore, (size_t)slots * n_buckets, bstride,
-                    (ops & (HX_AGG_MIN | HX_AGG_MAX)) != 0));
-            if (plan.t_rep)
-                HIP_TRY(hx::launch_init_rep(
-                    s, plan.t_rep, 8ull * slots, plan.rep_stride,
                     (ops & (HX_AGG_MIN | HX_AGG_MAX)) != 0));
         } else {
             HIP_TRY(hx::launch_init_state_slab(
@@ -1724,17 +1693,12 @@ hx_status exec_plan(hx_prepared* P, DevPlan& plan, const hx_agg_spec* agg,
         A.n_buckets = n_buckets;
         A.bstride = bstride;
         A.bstore = plan.t_bstore;
-        A.skip = getenv("HX_SKIP") ? atoi(getenv("HX_SKIP")) : 0;
-        A.table = {nullptr, nullptr, nullptr, nullptr,
-                   nullptr, nullptr, nullptr, slots - 1,
-                   plan.t_slab, plan.slab_stride, plan.t_rep,
-                   plan.rep_stride};
+        A.table = agg_table(plan);
         A.fill_limit = (unsigned long long)(double(slots) * 0.85);
         A.fill = plan.d_counters + 0;
         A.overflow = plan.d_counters + 1;
         A.matched = plan.d_counters + 2;
         A.fallback = plan.d_counters + 3;
-        A.poll = getenv("HX_NO_POLL") ? 0 : 1;
 
         hx_status est = ensure_events(plan);
         if (est != HX_OK) return est;
@@ -1744,75 +1708,18 @@ hx_status exec_plan(hx_prepared* P, DevPlan& plan, const hx_agg_spec* agg,
             uint32_t ne = 1024;
             if (const char* e = getenv("HX_RANGE_NE"))
                 ne = (uint32_t)strtoul(e, nullptr, 10);
-            uint32_t interp = 1;   // HX_INTERP=0 reverts to mix64 slots
-            if (const char* ie = getenv("HX_INTERP"))
-                interp = (uint32_t)atoi(ie);
             hx::RangeAux R{plan.d_range_bounds, plan.d_bound_rows,
                            plan.d_sst_rgs,     plan.d_sst_rg_off,
                            plan.d_sst_rg_cnt,  (uint32_t)plan.ssts.size(),
-                           plan.range_nblocks, ne,
-                           interp};
-            // HX_RANGE2: pair-load variant (16 B/lane dwordx4 loads, the
-            // dedup successor from registers/one shuffle, in-lane pair
-            // merge, direct LDS updates). Default ON since the fill-counter
-            // fix: with updates cheap its lighter scan wins — 5.3 ms vs the
-            // shuffle-pre-reduce kernel's 7.4 at the 1B shape (before the
-            // fix the relation was reversed: 25.4 vs 23.6).
-            const bool r2k = [] {
-                const char* e = getenv("HX_RANGE2");
-                return e ? atoi(e) != 0 : true;
-            }();
-            hipError_t re2 =
-                r2k ? hx::launch_scan_agg_range2(
-                          s, A, R, (ops & (HX_AGG_MIN | HX_AGG_MAX)) != 0)
-                    : hx::launch_scan_agg_range(
-                          s, A, R, (ops & (HX_AGG_MIN | HX_AGG_MAX)) != 0);
+                           plan.range_nblocks, ne};
+            hipError_t re2 = hx::launch_scan_agg_range2(
+                s, A, R, (ops & (HX_AGG_MIN | HX_AGG_MAX)) != 0);
             if (re2 != hipSuccess)
                 return fail(HX_ERR_HIP,
                             std::string("range kernel launch failed: ") +
                                 hipGetErrorString(re2));
         }
-        // the LDS-gang variant measured slower than the wave kernel at every
-        // tested config (see profiles/README r01 notes); opt-in for further
-        // experiments
-        bool use_gang = !use_range && !bucket &&
-                        getenv("HX_GANG_ON") != nullptr;
-        if (use_gang) {
-            // gang = number of SSTs in the dominant size class: one gang
-            // then covers EXACTLY one aligned series window (the transposed
-            // walk's register-combining + LDS-table-capacity contract)
-            uint32_t gang = 1;
-            {
-                std::map<int64_t, int> class_count;
-                std::vector<int64_t> per_sst(plan.ssts.size(), 0);
-                for (const auto& rd : plan.rgs) {
-                    int64_t end = rd.row_base + rd.n_rows;
-                    if (end > per_sst[rd.sst_id]) per_sst[rd.sst_id] = end;
-                }
-                for (int64_t rows : per_sst) class_count[rows]++;
-                int best = 0;
-                for (auto& [rows, cnt] : class_count)
-                    if (cnt > best) best = cnt;
-                gang = best > 0 ? (uint32_t)best : 1;
-            }
-            if (const char* ge = getenv("HX_GANG"))
-                gang = (uint32_t)strtoul(ge, nullptr, 10);
-            if (!plan.d_params) {
-                HIP_TRY(hipMalloc(&plan.d_params, 512));
-                if (hipHostMalloc(&plan.h_params, 512, hipHostMallocDefault)
-                    != hipSuccess)
-                    plan.h_params = malloc(512);
-            }
-            hipError_t ge2 = hx::launch_scan_agg_gang(
-                s, A, gang, (ops & (HX_AGG_MIN | HX_AGG_MAX)) != 0,
-                (hx::GangParams*)plan.h_params,
-                (hx::GangParams*)plan.d_params);
-            if (ge2 != hipSuccess)
-                return fail(HX_ERR_HIP,
-                            std::string("gang kernel launch failed: ") +
-                                hipGetErrorString(ge2));
-        }
-        if (!use_range && !use_gang)
+        if (!use_range)
             HIP_TRY(hx::launch_scan_agg(s, A, 0));
         HIP_TRY(hipEventRecord(e1, s));
         HIP_TRY(hipStreamSynchronize(s));
@@ -1861,13 +1768,10 @@ hx_status exec_plan(hx_prepared* P, DevPlan& plan, const hx_agg_spec* agg,
     if (cap64 > 0xFFFFFFFFull)
         return fail(HX_ERR_UNSUPPORTED, "result exceeds 2^32 groups");
     const uint32_t n = (uint32_t)cap64;
-    const bool aos = plan.t_slab != nullptr;
-    const bool has_sum = aos ? (ops & (HX_AGG_SUM | HX_AGG_AVG)) != 0
-                             : plan.t_sum != nullptr;
-    const bool has_cnt = aos ? (ops & (HX_AGG_COUNT | HX_AGG_AVG)) != 0
-                             : plan.t_cnt != nullptr;
-    const bool has_min = aos ? (ops & HX_AGG_MIN) != 0 : plan.t_min != nullptr;
-    const bool has_max = aos ? (ops & HX_AGG_MAX) != 0 : plan.t_max != nullptr;
+    const bool has_sum = (ops & (HX_AGG_SUM | HX_AGG_AVG)) != 0;
+    const bool has_cnt = (ops & (HX_AGG_COUNT | HX_AGG_AVG)) != 0;
+    const bool has_min = (ops & HX_AGG_MIN) != 0;
+    const bool has_max = (ops & HX_AGG_MAX) != 0;
     const bool has_avg = (agg->ops & HX_AGG_AVG) != 0;
     const uint32_t n_core = 1 + (bucket ? 1 : 0) + has_sum + has_cnt +
                             has_min + has_max;
@@ -1901,11 +1805,7 @@ hx_status exec_plan(hx_prepared* P, DevPlan& plan, const hx_agg_spec* agg,
 
     HIP_TRY(hipMemsetAsync(d_nout, 0, 8, s));
     hx::CompactOut co{c_series, c_bucket, c_sum, c_cnt, c_min, c_max, d_nout};
-    hx::AggTable T{nullptr, nullptr, nullptr, nullptr,
-                   nullptr, nullptr, nullptr, plan.slots - 1,
-                   plan.t_slab, plan.slab_stride, plan.t_rep,
-                   plan.rep_stride};
-    HIP_TRY(hx::launch_compact(s, T, plan.slots, ops, key_claim,
+    HIP_TRY(hx::launch_compact(s, agg_table(plan), plan.slots, key_claim,
                                bucket ? agg->bucket_ms : 0, lo_bucket,
                                n_buckets, bstride, plan.t_bstore, co,
                                compact_scratch));
@@ -2268,7 +2168,7 @@ extern "C" hx_status hx_scan(hx_handle* h, const hx_scan_spec* spec,
     HIP_TRY(hipMemsetAsync(d_cursor, 0, 8, s));
     hx::AggParams A = base_params(P, plan);
     if (append) {
-        A.skip = 2;   // keep every row: groups concatenate
+        A.keep_dups = 1;   // keep every row: groups concatenate
         // the packed (seq << 32 | row) sort key needs seq < 2^32
         for (const auto& c : h->ssts)
             if (c.seq >= (1ull << 32))

@@ -52,26 +52,18 @@ struct ClusterDev {
     int32_t n;
 };
 
-// Aggregate hash table: open addressing, linear probe.
-// state: 0 empty, 1 claim in flight, 2 ready (key words valid).
+// Aggregate hash table: open addressing, linear probe, one slab of
+// fixed-stride slots (probe + update touch one cache line). Two slot forms:
+//   key-claim (AggParams::key_claim): {key, sum, cnt[, min, max]}, stride
+//     32/64; key == KEY_EMPTY marks a free slot, claimed by one CAS.
+//   state-word: {state u32, pad, series, bucket, sum, cnt[, min, max]},
+//     stride 48/64; state: 0 empty, 1 claim in flight, 2 ready (key words
+//     valid).
+// min/max are ordered-u64 mapped f64 (bit-exact min/max).
 struct AggTable {
-    uint64_t* series;
-    int64_t*  bucket;        // null if bucket_ms == 0
-    uint32_t* state;
-    double*   sum;
-    unsigned long long* cnt;
-    unsigned long long* vmin;  // ordered-u64 mapped f64 (bit-exact min/max)
-    unsigned long long* vmax;
     uint32_t  mask;            // slots-1 (power of two)
-    // key-claim AoS mode: slot i = slab[i*stride .. ) = {key, sum, cnt
-    // [, min, max]} — probe + update touch ONE cache line instead of three
-    uint8_t*  slab;            // non-null => AoS mode (series-only grouping)
-    uint32_t  stride;          // 32 (sum/cnt) or 64 (with min/max)
-    // optional per-XCD accumulator replicas (HX_XCD_REP): keys live in the
-    // shared slab; each XCD's blocks accumulate into their own replica to
-    // avoid cross-L2 line ping-pong; compact merges the replicas.
-    uint8_t*  rep;             // 8 replicas x slots x rep_stride, or null
-    uint32_t  rep_stride;      // 16 (sum,cnt) or 32 (+min,max)
+    uint8_t*  slab;
+    uint32_t  stride;
 };
 
 struct AggParams {
@@ -91,7 +83,7 @@ struct AggParams {
     int64_t bucket_ms;             // 0 = group by series only
     uint32_t ops;                  // HX_AGG_* mask
     int32_t key_claim;             // 1 = one-CAS key-claim mode (no state word)
-    int32_t skip;                  // debug bisect: 1 skip table, 2 also skip dedup
+    int32_t keep_dups;             // 1 = Append: no dedup, every filtered row survives
     AggTable table;
     // direct-indexed bucket mode (bucket_ms > 0, key-claim safe, bucket
     // range known from the scan range): table keyed by series only; each
@@ -105,11 +97,9 @@ struct AggParams {
     unsigned long long* overflow;  // !=0 => rerun with a larger table
     unsigned long long* matched;   // rows surviving filter+dedup
     unsigned long long* fallback;  // LDS-table misses routed to global RMWs
-    int32_t poll;                  // 0 = no saturation poll in range kernel
-    int32_t _pad2;
 };
 
-// Series-range partitioned aggregation (k_scan_agg_range): the
+// Series-range partitioned aggregation (k_scan_agg_range2): the
 // series space is split at equal-sample quantile boundaries; block b owns
 // series in [bounds[b], bounds[b+1]) across ALL SSTs, accumulating into an
 // LDS table flushed once — global-table RMWs drop from one per 64-row-
@@ -123,13 +113,12 @@ struct RangeAux {
     const int32_t* sst_rg_cnt;   // per SST: count
     uint32_t n_ssts;
     uint32_t n_blocks;
-    uint32_t ne;                 // LDS hash slots (power of two)
-    // 1 = interpolation slots: first probe at (s-lo)*ne/(hi-lo) within the
-    // block's series range — ascending heads probe ascending slots, so the
-    // wave's DS accesses land on consecutive banks (conflict-free) instead
-    // of random ones, and collisions stay rare (series values are hashes,
-    // ~uniform in value). 0 = mix64 hashing.
-    uint32_t interp;
+    // LDS table slots (power of two). A key's first probe is its fractional
+    // position (s-lo)*ne/(hi-lo) within the block's series range — ascending rows
+    // probe ascending slots, so the wave's DS accesses land on consecutive
+    // banks (conflict-free) instead of random ones, and collisions stay rare
+    // (series values are hashes, ~uniform in value).
+    uint32_t ne;
 };
 
 // DELTA_BINARY_PACKED decode unit: one page -> dense i64 at dst_off (dec).

@@ -28,12 +28,9 @@ hipError_t launch_snappy(hipStream_t s, const uint8_t* blob, uint8_t* dec,
 hipError_t launch_copy_u64(hipStream_t s, const uint8_t* blob, uint8_t* dec,
                            const CopyDesc* descs, uint32_t n_descs);
 hipError_t launch_scan_agg(hipStream_t s, const AggParams& p, uint32_t grid);
-struct GangParams;  // kernels.hip internal; caller provides param buffers
-hipError_t launch_scan_agg_gang(hipStream_t s, const AggParams& p,
-                                uint32_t gang_size, bool minmax,
-                                GangParams* h_params, GangParams* d_params);
 // Series-range mode: sample series for quantile boundaries,
-// precompute per-(block,sst) row bounds, then the LDS-table range kernel.
+// precompute per-(block,sst) row bounds, then the LDS-table range kernel
+// (k_scan_agg_range2; the name is kept so the profiles/ records match).
 hipError_t launch_sample_series(hipStream_t s, const RgDesc* rgs,
                                 uint32_t n_rgs, const uint8_t* blob,
                                 const uint8_t* dec, uint64_t* out);
@@ -41,8 +38,6 @@ hipError_t launch_range_bounds(hipStream_t s, const AggParams& p,
                                const RangeAux& r, uint64_t* out);
 hipError_t launch_scan_agg_range2(hipStream_t s, const AggParams& p,
                                   const RangeAux& r, bool minmax);
-hipError_t launch_scan_agg_range(hipStream_t s, const AggParams& p,
-                                 const RangeAux& r, bool minmax);
 hipError_t launch_scan_rows(hipStream_t s, const AggParams& p,
                             uint32_t rg_first, uint32_t rg_last,
                             uint64_t* out_series, long long* out_ts,
@@ -54,10 +49,11 @@ hipError_t launch_gather_multi(hipStream_t s,
                                const unsigned long long* const* srcs,
                                uint32_t n_arrays, const uint32_t* perm,
                                unsigned long long* dst, uint32_t n);
-// scratch: device buffer of 2*grid_for(n_slots,256) u32 (two-phase compact
-// counts+bases); null routes to the single-pass kernel.
+// Live slots -> dense unsorted arrays. n_buckets == 0: two-phase (count,
+// scan, write) using scratch, a device buffer of 2*2048 u32 (per-block
+// counts + bases). n_buckets > 0: single-pass sweep, scratch unused.
 hipError_t launch_compact(hipStream_t s, const AggTable& t, uint32_t n_slots,
-                          uint32_t ops, int32_t key_claim, int64_t bucket_ms,
+                          int32_t key_claim, int64_t bucket_ms,
                           int64_t lo_bucket, uint32_t n_buckets,
                           uint32_t bstride, const uint8_t* bstore,
                           const CompactOut& o, uint32_t* scratch);
@@ -69,8 +65,10 @@ hipError_t launch_avg(hipStream_t s, const double* sum,
 hipError_t launch_iota(hipStream_t s, uint32_t* out, uint32_t n);
 hipError_t launch_init_slab(hipStream_t s, uint8_t* slab, uint32_t n_slots,
                             uint32_t stride);
-hipError_t launch_init_rep(hipStream_t s, uint8_t* rep, size_t total_slots,
-                           uint32_t stride, bool mm);
+// direct-indexed bucket store: total_rows accumulator rows of {sum, cnt
+// [, min, max]} (stride 16/32)
+hipError_t launch_init_accum_rows(hipStream_t s, uint8_t* rows,
+                                  size_t total_rows, uint32_t stride, bool mm);
 hipError_t launch_init_state_slab(hipStream_t s, uint8_t* slab,
                                   uint32_t n_slots, uint32_t stride, bool mm);
 hipError_t launch_seg_keys(hipStream_t s, const long long* ts, long long seg_ms,

@@ -101,14 +101,8 @@ __device__ __forceinline__ uint64_t row_seq(const AggParams& P,
         : sst.seq;
 }
 
-// Open-addressing claim + update. state: 0 empty / 1 claiming / 2 ready.
-// Claim via CAS on the state word (works for any 8/16-byte key — no key
-// sentinel needed); claimer stores key words then releases state=2; readers
-// are gated by the control dependency on state==2 (all table words accessed
-// with agent-scope atomics => L2-coherent, no L1 staleness).
-// accumulate into slot i: the shared slab, or this XCD's replica when
-// per-XCD replication is on (the replica's lines stay exclusive to one L2
-// — no cross-XCD ping-pong on the hot accumulator lines)
+// accumulate into key-claim slot i: its slab accumulators, or (direct-
+// indexed bucket mode) bucket b's row of the slot's dense accumulator rows
 __device__ __forceinline__ void keycas_add(const AggParams& P, uint32_t i,
                                            int64_t b, double vsum,
                                            unsigned long long cnt, double mn,
@@ -125,13 +119,6 @@ __device__ __forceinline__ void keycas_add(const AggParams& P, uint32_t i,
             return;
         }
         slot = P.bstore + ((size_t)i * P.n_buckets + (size_t)bi) * P.bstride;
-        off8 = 0; off16 = 8; off24 = 16; off32 = 24;
-    } else if (P.table.rep) {
-        uint32_t xcc;
-        asm("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        xcc &= 7u;
-        slot = P.table.rep +
-               ((size_t)xcc * (P.table.mask + 1ull) + i) * P.table.rep_stride;
         off8 = 0; off16 = 8; off24 = 16; off32 = 24;
     } else {
         slot = P.table.slab + (size_t)i * P.table.stride;
@@ -176,7 +163,7 @@ __device__ __forceinline__ void agg_update_keycas(const AggParams& P, uint64_t s
                 // P.fill is ONE word: per-claim increments serialize at the
                 // coherence point and backpressure the whole vmcnt pipeline
                 // (measured ~17 ms of the 24 ms launch). Callers that count
-                // claims in bulk (the range kernels' flush) pass
+                // claims in bulk (the range kernel's flush) pass
                 // count_fill = false and add per-block totals instead.
                 if (count_fill)
                     __hip_atomic_fetch_add(P.fill, 1ull, RLX, AGT);
@@ -210,11 +197,13 @@ k_init_state_slab(uint8_t* slab, uint32_t n_slots, uint32_t stride,
     }
 }
 
+// direct-indexed bucket store init: rows of {sum, cnt[, min, max]}
 extern "C" __global__ void __launch_bounds__(256)
-k_init_rep(uint8_t* rep, size_t total_slots, uint32_t stride, uint32_t mm) {
-    for (size_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total_slots;
+k_init_accum_rows(uint8_t* rows, size_t total_rows, uint32_t stride,
+                  uint32_t mm) {
+    for (size_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total_rows;
          i += (size_t)blockDim.x * gridDim.x) {
-        uint8_t* slot = rep + i * stride;
+        uint8_t* slot = rows + i * stride;
         ((uint64_t*)slot)[0] = 0;   // sum
         ((uint64_t*)slot)[1] = 0;   // cnt
         if (mm) {
@@ -316,7 +305,7 @@ __device__ __forceinline__ bool row_alive(const AggParams& P, const RgDesc& rg,
                                           uint32_t n, uint64_t s, int64_t t) {
     bool alive = (t >= P.ts_lo) & (t < P.ts_hi);
     if (alive && P.use_sset) alive = sset_has(P, s);
-    if (alive && P.skip < 2) {   // skip>=2: Append keeps every row
+    if (alive && !P.keep_dups) {
         // within-SST dedup: the LAST row of an equal-PK run survives
         // (LastValueOperator, operator.rs:37-44; plan order read.rs:456-480)
         bool dup = false;
@@ -385,7 +374,7 @@ __device__ __forceinline__ void scan_window(const AggParams& P,
     if (inb) {
         alive = (t >= P.ts_lo) & (t < P.ts_hi);
         if (alive && P.use_sset) alive = sset_has(P, s);
-        if (alive && P.skip < 2) {
+        if (alive && !P.keep_dups) {
             bool dup = false;
             if (has_next) {
                 dup = (s1 == s) & (t1 == t);
@@ -512,290 +501,6 @@ k_scan_agg(AggParams P) {
 }
 
 // ---------------------------------------------------------------------------
-// Gang kernel (series-only grouping): one workgroup aggregates a GANG of
-// same-ordinal row groups from many SSTs into an LDS hash table, then
-// flushes distinct keys to the global table. Same-ordinal row groups cover
-// roughly the same series window (SSTs are PK-sorted over one id universe),
-// so a series touched by G SSTs costs ONE global update instead of G —
-// global atomic traffic drops by ~G (guideline 12 at gang scale).
-// ---------------------------------------------------------------------------
-struct GangParams {
-    AggParams P;
-    uint32_t gang_size;
-    uint32_t n_gangs;
-    uint32_t ne;        // LDS hash entries (power of two)
-    uint32_t has_mm;    // min/max tracked
-};
-
-template <bool MM>
-__device__ __forceinline__ void lds_update(const AggParams& P, uint64_t* lkey,
-                                           double* lsum, unsigned int* lcnt,
-                                           unsigned long long* lmin,
-                                           unsigned long long* lmax,
-                                           uint32_t ne, uint64_t sv, double v,
-                                           uint32_t cnt, double mn, double mx,
-                                           uint32_t i0 = 0xFFFFFFFFu,
-                                           uint64_t pre = 0,
-                                           bool has_pre = false) {
-    uint32_t i = (i0 != 0xFFFFFFFFu) ? i0 : ((uint32_t)mix64(sv) & (ne - 1));
-    // bisect modes (wrong results; cost decomposition only):
-    // skip=5 probe-read only, no atomics; skip=6 atomics to the probe slot
-    // without key verification
-    if (P.skip == 5) {
-        if (lkey[i] == sv) return;
-        return;
-    }
-    if (P.skip == 6) {
-        atomicAdd(&lsum[i], v);
-        atomicAdd(&lcnt[i], cnt);
-        return;
-    }
-#pragma unroll 1
-    for (int probes = 0; probes < 16; probes++) {
-        // probe prefetch: the caller read slot i0 right after the row loads,
-        // so the common-case key check pays no fresh LDS round-trip on the
-        // update critical path. A stale EMPTY only re-routes through the
-        // CAS (keys transition EMPTY->key exactly once), never corrupts.
-        uint64_t kk = (has_pre && probes == 0) ? pre : lkey[i];
-        if (kk == KEY_EMPTY) {
-            uint64_t old = atomicCAS(&lkey[i], KEY_EMPTY, sv);
-            kk = (old == KEY_EMPTY) ? sv : old;
-        }
-        if (kk == sv) {
-            atomicAdd(&lsum[i], v);
-            atomicAdd(&lcnt[i], cnt);
-            if (MM) {
-                atomicMin(&lmin[i], f64_ordered(mn));
-                atomicMax(&lmax[i], f64_ordered(mx));
-            }
-            return;
-        }
-        i = (i + 1) & (ne - 1);
-    }
-    // LDS table full: direct global update (count it — a non-trivial rate
-    // here turns the kernel into a global-RMW storm; wave-aggregated so the
-    // counter itself cannot serialize)
-    if (P.fallback) {
-        const unsigned long long mk = __ballot(1);
-        const int lane = (int)(threadIdx.x & 63);
-        if ((__ffsll(mk) - 1) == lane)
-            __hip_atomic_fetch_add(P.fallback,
-                                   (unsigned long long)__popcll(mk), RLX, AGT);
-    }
-    agg_update(P, sv, 0, v, cnt, mn, mx);
-}
-
-template <bool MM>
-__global__ void __launch_bounds__(1024)
-k_scan_agg_gang(const GangParams* __restrict__ gp,
-                const uint8_t* __restrict__ blob_arg,
-                const uint8_t* __restrict__ dec_arg,
-                const RgDesc* __restrict__ rgs_arg) {
-    // blob/dec/rgs come as KERNEL ARGUMENTS: pointers loaded from memory are
-    // generic (flat_load — slow); argument pointers keep the global address
-    // space (global_load).
-    const GangParams& G = *gp;
-    // Param handling: ~12 hot scalars live in SGPRs; everything the cold
-    // paths need (table pointers, cluster arrays, counters) is mirrored
-    // into LDS once per block — neither SGPR spills (by-value struct) nor
-    // per-iteration s_load stalls (pointer chasing).
-    const uint8_t* const blob = blob_arg;
-    const uint8_t* const dec = dec_arg;
-    const int64_t ts_lo = G.P.ts_lo, ts_hi = G.P.ts_hi;
-    const int32_t skip = G.P.skip;
-    const int32_t use_sset = G.P.use_sset;
-    const uint32_t gang_size = G.gang_size;
-    const uint32_t n_gangs = G.n_gangs;
-    const uint32_t n_rgs_all = G.P.n_rgs;
-    const RgDesc* const rgs_all = rgs_arg;
-    const SstDev* const ssts_all = G.P.ssts;
-    unsigned long long* const matched_ptr = G.P.matched;
-    // Transposed gang walk: a thread owns TWO row positions of the aligned
-    // series window and visits them across every unit (row-group slice) of
-    // the gang. Same-size SSTs slice into EXACTLY aligned units, so the
-    // series at a fixed row position is constant across them — the thread
-    // accumulates in registers and touches the LDS table only when the key
-    // changes. Loads stay coalesced (lanes = consecutive rows) and the
-    // unit-loop iterations are independent (memory-level parallelism).
-    // Alignment is a speed matter only: register combining merges equal
-    // ADJACENT keys, which is correct for any data.
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const uint32_t ne = G.ne;
-    AggParams* Pm = (AggParams*)smem;          // LDS mirror for cold paths
-    RgDesc* ldesc = (RgDesc*)(smem + 320);
-    const size_t desc_bytes = 320 + (size_t)gang_size * sizeof(RgDesc);
-    uint64_t* lkey = (uint64_t*)(smem + desc_bytes);
-    double* lsum = (double*)(smem + desc_bytes + (size_t)ne * 8);
-    unsigned long long* lmin =
-        (unsigned long long*)(smem + desc_bytes + (size_t)ne * 16);
-    unsigned long long* lmax =
-        (unsigned long long*)(smem + desc_bytes + (size_t)ne * (MM ? 24 : 16));
-    unsigned int* lcnt =
-        (unsigned int*)(smem + desc_bytes + (size_t)ne * (MM ? 32 : 16));
-    {
-        static_assert(sizeof(AggParams) <= 320, "grow the LDS mirror");
-        const uint64_t* src = (const uint64_t*)&gp->P;
-        uint64_t* dst = (uint64_t*)Pm;
-        for (uint32_t i = threadIdx.x; i < sizeof(AggParams) / 8;
-             i += blockDim.x)
-            dst[i] = src[i];
-    }
-
-    const int lane = threadIdx.x & 63;
-    unsigned long long my_matched = 0;
-    unsigned long long my_flushes = 0;
-    for (uint32_t gang = blockIdx.x; gang < n_gangs; gang += gridDim.x) {
-        const uint32_t rg0 = gang * gang_size;
-        const uint32_t rg_end = min(rg0 + gang_size, n_rgs_all);
-        const uint32_t nu = rg_end - rg0;
-        for (uint32_t i = threadIdx.x; i < ne; i += blockDim.x) {
-            lkey[i] = KEY_EMPTY;
-            lsum[i] = 0.0;
-            lcnt[i] = 0u;
-            if (MM) {
-                lmin[i] = ~0ull;
-                lmax[i] = 0ull;
-            }
-        }
-        // preload unit descriptors (one dynamic-LDS object only — G17)
-        for (uint32_t u = threadIdx.x; u < nu; u += blockDim.x)
-            ldesc[u] = rgs_all[rg0 + u];
-        __syncthreads();
-        uint32_t max_n = 0;
-        for (uint32_t u = 0; u < nu; u++) max_n = max(max_n, ldesc[u].n_rows);
-
-        bool have_run = false;
-        uint64_t run_key = 0;
-        double run_sum = 0, run_min = 0, run_max = 0;
-        uint32_t run_cnt = 0;
-        for (uint32_t roff = 0; roff < max_n; roff += blockDim.x) {
-            const uint32_t r = roff + threadIdx.x;
-            // two-stage software pipeline over the units: issue unit u+1's
-            // column loads before processing unit u, so each iteration's
-            // dependent-load stall overlaps the next iteration's fetches
-            // (the compiler alone serializes them behind per-iteration
-            // waits — measured ~730 cy/iteration without this).
-            uint64_t sA = KEY_EMPTY, s1A = KEY_EMPTY;
-            int64_t tA = 0, t1A = 0;
-            double vA = 0;
-            uint32_t nA = 0, sstA = 0;
-            int32_t nxA = -1;
-            auto issue = [&](uint32_t u, uint64_t& s_, uint64_t& s1_,
-                             int64_t& t_, int64_t& t1_, double& v_,
-                             uint32_t& n_, uint32_t& sst_, int32_t& nx_) {
-                const RgDesc rg = ldesc[u];
-                n_ = rg.n_rows;
-                sst_ = rg.sst_id;
-                nx_ = rg.next_rg;
-                const bool inb = r < n_;
-                const bool inb1 = r + 1 < n_;
-                const uint64_t* S =
-                    (const uint64_t*)hx_ptr(blob, dec, rg.series_off);
-                const int64_t* T =
-                    (const int64_t*)hx_ptr(blob, dec, rg.ts_off);
-                const double* V =
-                    (const double*)hx_ptr(blob, dec, rg.val_off);
-                s_ = inb ? S[r] : KEY_EMPTY;
-                t_ = inb ? T[r] : 0;
-                v_ = inb ? V[r] : 0.0;
-                s1_ = inb1 ? S[r + 1] : KEY_EMPTY;
-                t1_ = inb1 ? T[r + 1] : 0;
-            };
-            if (nu > 0)
-                issue(0, sA, s1A, tA, t1A, vA, nA, sstA, nxA);
-#pragma unroll 1
-            for (uint32_t u = 0; u < nu; u++) {
-                uint64_t sB = KEY_EMPTY, s1B = KEY_EMPTY;
-                int64_t tB = 0, t1B = 0;
-                double vB = 0;
-                uint32_t nB = 0, sstB = 0;
-                int32_t nxB = -1;
-                if (u + 1 < nu)
-                    issue(u + 1, sB, s1B, tB, t1B, vB, nB, sstB, nxB);
-                const uint64_t sv = sA;
-                const int64_t tv = tA;
-                if (r < nA) {
-                    bool alive = (tv >= ts_lo) & (tv < ts_hi);
-                    if (alive && use_sset) alive = sset_has(*Pm, sv);
-                    if (alive && skip < 2) {
-                        bool dup = false;
-                        if (r + 1 < nA) {
-                            dup = (s1A == sv) & (t1A == tv);
-                        } else if (nxA >= 0) {
-                            const RgDesc nx = rgs_all[nxA];
-                            uint64_t s2 = *(const uint64_t*)hx_ptr(
-                                blob, dec, nx.series_off);
-                            int64_t t2 = *(const int64_t*)hx_ptr(blob, dec,
-                                                                 nx.ts_off);
-                            dup = (s2 == sv) & (t2 == tv);
-                        }
-                        if (!dup) {
-                            const SstDev sst = ssts_all[sstA];
-                            if (sst.cluster >= 0) {
-                                uint64_t msq = sst.dense_seq
-                                    ? ((const uint64_t*)(dec +
-                                           (sst.dense_seq & OFF_MASK)))
-                                          [ldesc[u].row_base + r]
-                                    : sst.seq;
-                                dup = shadowed(*Pm, sst, msq, sv, tv);
-                            }
-                        }
-                        alive = !dup;
-                    }
-                    if (alive) {
-                        const double v = vA;
-                        my_matched++;
-                        if (skip == 1 || skip == 2) {
-                        } else if (have_run && run_key == sv) {
-                            run_sum += v;
-                            run_cnt++;
-                            if (MM) {
-                                run_min = fmin(run_min, v);
-                                run_max = fmax(run_max, v);
-                            }
-                        } else {
-                            if (have_run) {
-                                if (skip == 3) my_flushes++;  // bisect
-                                else lds_update<MM>(*Pm, lkey, lsum, lcnt,
-                                                    lmin, lmax, ne, run_key,
-                                                    run_sum, run_cnt, run_min,
-                                                    run_max);
-                            }
-                            have_run = true;
-                            run_key = sv;
-                            run_sum = v;
-                            run_cnt = 1;
-                            run_min = v;
-                            run_max = v;
-                        }
-                    }
-                }
-                sA = sB; s1A = s1B; tA = tB; t1A = t1B; vA = vB;
-                nA = nB; sstA = sstB; nxA = nxB;
-            }
-        }
-        if (have_run) {
-            lds_update<MM>(*Pm, lkey, lsum, lcnt, lmin, lmax, ne, run_key,
-                           run_sum, run_cnt, run_min, run_max);
-            have_run = false;
-        }
-        __syncthreads();
-        for (uint32_t i = threadIdx.x; i < ne; i += blockDim.x) {
-            if (lkey[i] == KEY_EMPTY) continue;
-            agg_update(*Pm, lkey[i], 0, lsum[i], (unsigned long long)lcnt[i],
-                       MM ? ordered_f64(lmin[i]) : 0.0,
-                       MM ? ordered_f64(lmax[i]) : 0.0);
-        }
-        __syncthreads();
-    }
-    if (skip == 3) my_matched = my_flushes;  // bisect: report flush count
-    for (int off = 32; off > 0; off >>= 1)
-        my_matched += __shfl_down(my_matched, off, 64);
-    if ((threadIdx.x & 63) == 0 && my_matched)
-        atomicAdd(matched_ptr, my_matched);
-}
-
-// ---------------------------------------------------------------------------
 // Series-range partitioned aggregation. Position-aligned LDS
 // gangs lose to series-position jitter (sqrt-scale fluctuations between
 // SSTs dwarf a window), so the partition here is by series VALUE: block b
@@ -889,286 +594,66 @@ k_range_bounds(AggParams P, RangeAux R, uint64_t* __restrict__ out) {
     }
 }
 
-// 64-row window worker for the range kernel: like scan_window but per-wave
-// (lane-indexed rows), clamped to [base, hi) with successor dedup against
-// the slice's TRUE row count, and no global-table probe hint. Templated on
-// MM so the sum/count path never pays the min/max cross-lane shuffles
-// (each 64-bit __shfl is two ds_bpermutes — real LDS-array cycles).
-template <bool MM>
-__device__ __forceinline__ void scan_window_range(
-    const AggParams& P, const RgDesc& rg, const SstDev& sst,
-    const uint64_t* S, const int64_t* T, const double* V, uint32_t base,
-    uint32_t hi, uint32_t n_true, int lane, unsigned long long& my_matched,
-    WinResult& W, const uint64_t* lkey, uint32_t ne, uint32_t interp,
-    uint64_t ilo, double islope) {
-    const uint32_t r = base + (uint32_t)lane;
-    const bool inb = r < hi;
-    const bool has_next = r + 1 < n_true;
-    uint64_t s = KEY_EMPTY;
-    int64_t t = 0;
-    double v = 0.0;
-    uint64_t s1 = 0;
-    int64_t t1 = 0;
-    bool alive = false;
-    if (inb) {
-        t = T[r];
-        s = S[r];
-        v = V[r];
-        if (has_next) {
-            s1 = S[r + 1];
-            t1 = T[r + 1];
-        }
-    }
-    // probe prefetch: the head lane's LDS slot is known from `s` alone —
-    // issue the probe read NOW so its latency hides under filter/dedup
-    {
-        uint32_t slot;
-        if (interp) {
-            uint32_t x = (uint32_t)((double)(s - ilo) * islope);
-            slot = x < ne ? x : ne - 1;
-        } else {
-            slot = (uint32_t)mix64(s) & (ne - 1);
-        }
-        W.hint_i = slot;
-        W.hint_k = lkey[slot];
-    }
-    if (inb) {
-        alive = (t >= P.ts_lo) & (t < P.ts_hi);
-        if (alive && P.use_sset) alive = sset_has(P, s);
-        if (alive && P.skip < 2) {
-            bool dup = false;
-            if (has_next) {
-                dup = (s1 == s) & (t1 == t);
-            } else if (rg.next_rg >= 0) {
-                const RgDesc nx = P.rgs[rg.next_rg];
-                uint64_t s2 = *(const uint64_t*)hx_ptr(P.blob, P.dec,
-                                                       nx.series_off);
-                int64_t t2 = *(const int64_t*)hx_ptr(P.blob, P.dec, nx.ts_off);
-                dup = (s2 == s) & (t2 == t);
-            }
-            if (!dup && sst.cluster >= 0)
-            dup = shadowed(P, sst, row_seq(P, sst, rg, r), s, t);
-            alive = !dup;
-        }
-        if (!alive) v = 0.0;
-    }
-    unsigned long long c = alive ? 1ull : 0ull;
-    double vv = alive ? v : 0.0;
-    double mn = alive ? v : HUGE_VAL;
-    double mx = alive ? v : -HUGE_VAL;
-    my_matched += c;
-    if (P.skip == 4) {
-        // bisect mode: no wave pre-reduction — every alive lane updates the
-        // LDS table itself (short runs make the shfl loop VALU-heavy)
-        W.s = s;
-        W.b = 0;
-        W.vv = vv;
-        W.mn = mn;
-        W.mx = mx;
-        W.c = c;
-        W.head = alive;
-        return;
-    }
-    const uint64_t sp = __shfl_up(s, 1, 64);
-    const bool head = (lane == 0) || sp != s;
-    bool done = false;
-    for (int d = 1; d < 64; d++) {
-        const uint64_t s2 = __shfl_down(s, d, 64);
-        const double v2 = __shfl_down(vv, d, 64);
-        const unsigned long long c2 = __shfl_down(c, d, 64);
-        const double mn2 = MM ? __shfl_down(mn, d, 64) : 0.0;
-        const double mx2 = MM ? __shfl_down(mx, d, 64) : 0.0;
-        done = done || (lane + d >= 64) || s2 != s;
-        if (head && !done) {
-            vv += v2;
-            c += c2;
-            if (MM) {
-                mn = fmin(mn, mn2);
-                mx = fmax(mx, mx2);
-            }
-        }
-        if (__all(done)) break;
-    }
-    W.s = s;
-    W.b = 0;
-    W.vv = vv;
-    W.mn = mn;
-    W.mx = mx;
-    W.c = c;
-    W.head = head;
-}
-
-template <bool MM, int MINW>
-__global__ void __launch_bounds__(256, MINW)
-k_scan_agg_range(AggParams P, RangeAux R) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    __shared__ int s_abort;   // global table saturated: stop, host retries
-    const uint32_t ne = R.ne;
-    uint64_t* lkey = (uint64_t*)smem;
-    double* lsum = (double*)(smem + (size_t)ne * 8);
-    unsigned long long* lmin = (unsigned long long*)(smem + (size_t)ne * 16);
-    unsigned long long* lmax = (unsigned long long*)(smem + (size_t)ne * 24);
-    unsigned int* lcnt = (unsigned int*)(smem + (size_t)ne * (MM ? 32 : 16));
-    const int lane = threadIdx.x & 63;
-    const uint32_t wave = threadIdx.x >> 6;
-    const uint32_t n_waves = blockDim.x >> 6;
-    unsigned long long my_matched = 0;
-    for (uint32_t blk = blockIdx.x; blk < R.n_blocks; blk += gridDim.x) {
-        // saturation early-abort, ONCE PER BLOCK: P.fill's line is evicted
-        // chip-wide by every agent-scope claim, so ANY load of it is served
-        // at the coherence point (~88/us single-word) — polling per
-        // (wave, sst) serialized the whole kernel (+23 ms at the 1B shape).
-        // A stale read only delays the abort; the probe cap still bounds a
-        // doomed pass.
-        if (threadIdx.x == 0) {
-            s_abort = 0;
-            if (P.poll && (blk & 7u) == 0) {
-                unsigned long long f = __hip_atomic_load(
-                    P.fill, RLX, __HIP_MEMORY_SCOPE_WORKGROUP);
-                if (f > P.fill_limit) s_abort = 1;
-            }
-        }
-        for (uint32_t i = threadIdx.x; i < ne; i += blockDim.x) {
-            lkey[i] = KEY_EMPTY;
-            lsum[i] = 0.0;
-            lcnt[i] = 0u;
-            if (MM) {
-                lmin[i] = ~0ull;
-                lmax[i] = 0ull;
-            }
-        }
-        // interpolation slotting (R.interp): first probe at the key's
-        // fractional position within the block's series range. Heads arrive
-        // in ascending series order, so a wave's DS ops hit consecutive
-        // slots = consecutive banks (conflict-free); collisions fall back to
-        // linear probing as before.
-        double islope = 0.0;
-        uint64_t ilo = 0;
-        if (R.interp) {
-            ilo = R.bounds[blk];
-            const uint64_t ihi = R.bounds[blk + 1];
-            islope = (double)ne / ((double)(ihi - ilo) + 1.0);
-        }
-        __syncthreads();
-        if (s_abort) {
-            if (threadIdx.x == 0)
-                __hip_atomic_fetch_add(P.overflow, 1ull, RLX, AGT);
-            break;   // host retries with a larger table
-        }
-        for (uint32_t si = wave; si < R.n_ssts; si += n_waves) {
-            const int32_t loff = R.sst_rg_off[si];
-            const uint64_t pk0 = R.bound_rows[(size_t)blk * R.n_ssts + si];
-            const uint64_t pk1 =
-                R.bound_rows[(size_t)(blk + 1) * R.n_ssts + si];
-            uint32_t pos = (uint32_t)(pk0 >> 32);
-            uint32_t row = (uint32_t)pk0;
-            const uint32_t epos = (uint32_t)(pk1 >> 32);
-            const uint32_t erow = (uint32_t)pk1;
-            while (pos < epos || (pos == epos && row < erow)) {
-                const RgDesc rg = P.rgs[R.sst_rgs[loff + (int32_t)pos]];
-                const uint64_t* S =
-                    (const uint64_t*)hx_ptr(P.blob, P.dec, rg.series_off);
-                const int64_t* T =
-                    (const int64_t*)hx_ptr(P.blob, P.dec, rg.ts_off);
-                const double* V =
-                    (const double*)hx_ptr(P.blob, P.dec, rg.val_off);
-                const SstDev sst = P.ssts[rg.sst_id];
-                const uint32_t hi = (pos == epos) ? erow : rg.n_rows;
-                // dual 64-row windows: two independent load->reduce->LDS
-                // chains in flight per wave (quad measured equal-to-worse:
-                // the bound is not window-chain MLP)
-                for (uint32_t base = row; base < hi; base += 128) {
-                    WinResult A, B;
-                    B.c = 0;
-                    B.head = false;
-                    scan_window_range<MM>(P, rg, sst, S, T, V, base, hi,
-                                          rg.n_rows, lane, my_matched, A,
-                                          lkey, ne, R.interp, ilo, islope);
-                    if (base + 64 < hi)
-                        scan_window_range<MM>(P, rg, sst, S, T, V, base + 64,
-                                              hi, rg.n_rows, lane, my_matched,
-                                              B, lkey, ne, R.interp, ilo,
-                                              islope);
-                    if (P.skip == 1) continue;
-                    // verified-hit short circuit: the probe read happened at
-                    // load time; hint_k == key PROVES the slot (keys are
-                    // write-once), so the adds go straight to LDS with no
-                    // fresh read and no probe-loop control flow — the loop
-                    // structure alone measured ~19.5 ms of the 23.9 ms
-                    // kernel (skip6 bisect)
-                    if (A.head && A.c > 0) {
-                        if (A.hint_k == A.s) {
-                            atomicAdd(&lsum[A.hint_i], A.vv);
-                            atomicAdd(&lcnt[A.hint_i], (uint32_t)A.c);
-                            if (MM) {
-                                atomicMin(&lmin[A.hint_i], f64_ordered(A.mn));
-                                atomicMax(&lmax[A.hint_i], f64_ordered(A.mx));
-                            }
-                        } else {
-                            lds_update<MM>(P, lkey, lsum, lcnt, lmin, lmax,
-                                           ne, A.s, A.vv, (uint32_t)A.c,
-                                           A.mn, A.mx, A.hint_i);
-                        }
-                    }
-                    if (B.head && B.c > 0) {
-                        if (B.hint_k == B.s) {
-                            atomicAdd(&lsum[B.hint_i], B.vv);
-                            atomicAdd(&lcnt[B.hint_i], (uint32_t)B.c);
-                            if (MM) {
-                                atomicMin(&lmin[B.hint_i], f64_ordered(B.mn));
-                                atomicMax(&lmax[B.hint_i], f64_ordered(B.mx));
-                            }
-                        } else {
-                            lds_update<MM>(P, lkey, lsum, lcnt, lmin, lmax,
-                                           ne, B.s, B.vv, (uint32_t)B.c,
-                                           B.mn, B.mx, B.hint_i);
-                        }
-                    }
-                }
-                pos++;
-                row = 0;
-            }
-        }
-        __syncthreads();
-        {
-            unsigned long long live = 0;
-            for (uint32_t i = threadIdx.x; i < ne; i += blockDim.x) {
-                if (lkey[i] == KEY_EMPTY) continue;
-                live++;
-                agg_update(P, lkey[i], 0, lsum[i],
-                           (unsigned long long)lcnt[i],
-                           MM ? ordered_f64(lmin[i]) : 0.0,
-                           MM ? ordered_f64(lmax[i]) : 0.0, 0xFFFFFFFFu, 0,
-                           false);
-            }
-            for (int off = 32; off > 0; off >>= 1)
-                live += __shfl_down(live, off, 64);
-            if ((threadIdx.x & 63) == 0 && live)
-                __hip_atomic_fetch_add(P.fill, live, RLX, AGT);
-        }
-        __syncthreads();
-    }
-    for (int off = 32; off > 0; off >>= 1)
-        my_matched += __shfl_down(my_matched, off, 64);
-    if ((threadIdx.x & 63) == 0 && my_matched)
-        atomicAdd(P.matched, my_matched);
-}
-
 // ---------------------------------------------------------------------------
-// Pair-load series-range kernel (round-2 redesign of k_scan_agg_range).
-// The r01 kernel was 95% SQ_WAIT_ANY at ~2% LDS-array utilization: pure
-// latency exposure, not throughput. This variant removes latency sources:
+// Pair-load series-range kernel. Its predecessor (one row per lane, wave
+// shuffle pre-reduction) was 95% SQ_WAIT_ANY at ~2% LDS-array
+// utilization: pure latency exposure, not throughput. This kernel removes
+// latency sources:
 //   - 16 B/lane dwordx4 loads (the calibrated wide-stream width): each lane
 //     owns TWO consecutive rows, halving load instructions per row;
 //   - the successor row for dedup comes from the register pair / one
 //     cross-lane shuffle instead of a second global read of S and T;
 //   - NO cross-lane run pre-reduction (measured ±3%): each lane merges its
 //     own pair in registers (36% of adjacent rows share a series at the
-//     headline shape) and issues its 1-2 LDS updates directly — the shuffle
-//     loop's ~7 dependent ds_bpermute rounds per window disappear.
-// Table layout, partitioning, flush and dedup semantics are identical to
-// k_scan_agg_range.
+//     headline shape) and issues its 1-2 LDS updates directly.
+// Per block: reset the LDS table, scan the block's series range in every
+// SST, flush each live LDS slot to the global table once.
 // ---------------------------------------------------------------------------
+
+// Add one (key, partial aggregate) to the block's LDS table, first probe at
+// slot i. `pre` is lkey[i] as the caller read it right after the row loads,
+// so the common-case key check pays no fresh LDS round-trip on the update
+// critical path. A stale EMPTY only re-routes through the CAS (keys
+// transition EMPTY->key exactly once), never corrupts.
+template <bool MM>
+__device__ __forceinline__ void lds_update(const AggParams& P, uint64_t* lkey,
+                                           double* lsum, unsigned int* lcnt,
+                                           unsigned long long* lmin,
+                                           unsigned long long* lmax,
+                                           uint32_t ne, uint64_t sv, double v,
+                                           uint32_t cnt, double mn, double mx,
+                                           uint32_t i, uint64_t pre) {
+#pragma unroll 1
+    for (int probes = 0; probes < 16; probes++) {
+        uint64_t kk = (probes == 0) ? pre : lkey[i];
+        if (kk == KEY_EMPTY) {
+            uint64_t old = atomicCAS(&lkey[i], KEY_EMPTY, sv);
+            kk = (old == KEY_EMPTY) ? sv : old;
+        }
+        if (kk == sv) {
+            atomicAdd(&lsum[i], v);
+            atomicAdd(&lcnt[i], cnt);
+            if (MM) {
+                atomicMin(&lmin[i], f64_ordered(mn));
+                atomicMax(&lmax[i], f64_ordered(mx));
+            }
+            return;
+        }
+        i = (i + 1) & (ne - 1);
+    }
+    // LDS table full: direct global update (count it — a non-trivial rate
+    // here turns the kernel into a global-RMW storm; wave-aggregated so the
+    // counter itself cannot serialize)
+    if (P.fallback) {
+        const unsigned long long mk = __ballot(1);
+        const int lane = (int)(threadIdx.x & 63);
+        if ((__ffsll(mk) - 1) == lane)
+            __hip_atomic_fetch_add(P.fallback,
+                                   (unsigned long long)__popcll(mk), RLX, AGT);
+    }
+    agg_update(P, sv, 0, v, cnt, mn, mx);
+}
+
 template <bool MM>
 __global__ void __launch_bounds__(256)
 k_scan_agg_range2(AggParams P, RangeAux R) {
@@ -1185,9 +670,15 @@ k_scan_agg_range2(AggParams P, RangeAux R) {
     const uint32_t n_waves = blockDim.x >> 6;
     unsigned long long my_matched = 0;
     for (uint32_t blk = blockIdx.x; blk < R.n_blocks; blk += gridDim.x) {
+        // saturation early-abort, polled by ONE thread per block on every
+        // 8th block: P.fill's line is evicted chip-wide by every agent-scope
+        // claim, so ANY load of it is served at the coherence point (~88/us
+        // single-word) — polling per (wave, sst) serialized the whole kernel
+        // (+23 ms at the 1B shape). A stale read only delays the abort; the
+        // probe cap still bounds a doomed pass.
         if (threadIdx.x == 0) {
             s_abort = 0;
-            if (P.poll && (blk & 7u) == 0) {
+            if ((blk & 7u) == 0) {
                 unsigned long long f = __hip_atomic_load(
                     P.fill, RLX, __HIP_MEMORY_SCOPE_WORKGROUP);
                 if (f > P.fill_limit) s_abort = 1;
@@ -1202,18 +693,16 @@ k_scan_agg_range2(AggParams P, RangeAux R) {
                 lmax[i] = 0ull;
             }
         }
-        double islope = 0.0;
-        uint64_t ilo = 0;
-        if (R.interp) {
-            ilo = R.bounds[blk];
-            const uint64_t ihi = R.bounds[blk + 1];
-            islope = (double)ne / ((double)(ihi - ilo) + 1.0);
-        }
+        // slot of a key = its fractional position within the block's series
+        // range (RangeAux::ne); collisions fall back to linear probing
+        const uint64_t ilo = R.bounds[blk];
+        const uint64_t ihi = R.bounds[blk + 1];
+        const double islope = (double)ne / ((double)(ihi - ilo) + 1.0);
         __syncthreads();
         if (s_abort) {
             if (threadIdx.x == 0)
                 __hip_atomic_fetch_add(P.overflow, 1ull, RLX, AGT);
-            break;
+            break;   // host retries with a larger table
         }
         for (uint32_t si = wave; si < R.n_ssts; si += n_waves) {
             const int32_t loff = R.sst_rg_off[si];
@@ -1261,16 +750,12 @@ k_scan_agg_range2(AggParams P, RangeAux R) {
                     }
                     // slot + probe prefetch: issue the LDS probe reads NOW
                     // so their ~50-cycle latency hides under filter/dedup
-                    uint32_t iA, iB;
-                    if (R.interp) {
-                        uint32_t x0 = (uint32_t)((double)(s0 - ilo) * islope);
-                        uint32_t x1 = (uint32_t)((double)(s1 - ilo) * islope);
-                        iA = x0 < ne ? x0 : ne - 1;
-                        iB = x1 < ne ? x1 : ne - 1;
-                    } else {
-                        iA = (uint32_t)mix64(s0) & (ne - 1);
-                        iB = (uint32_t)mix64(s1) & (ne - 1);
-                    }
+                    const uint32_t x0 =
+                        (uint32_t)((double)(s0 - ilo) * islope);
+                    const uint32_t x1 =
+                        (uint32_t)((double)(s1 - ilo) * islope);
+                    const uint32_t iA = x0 < ne ? x0 : ne - 1;
+                    const uint32_t iB = x1 < ne ? x1 : ne - 1;
                     const uint64_t preA = lkey[iA];
                     const uint64_t preB = lkey[iB];
                     // window validity: [max(row, base), hi)
@@ -1286,7 +771,7 @@ k_scan_agg_range2(AggParams P, RangeAux R) {
                     // pair); lane 63 / slice-tail fall back to scalar loads
                     const uint64_t sn = __shfl_down(s0, 1, 64);
                     const int64_t tn = __shfl_down((long long)t0, 1, 64);
-                    if (a0 && P.skip < 2) {
+                    if (a0 && !P.keep_dups) {
                         bool dup;
                         if (r1 < nt) {
                             dup = (s1 == s0) & (t1 == t0);
@@ -1304,7 +789,7 @@ k_scan_agg_range2(AggParams P, RangeAux R) {
                                            s0, t0);
                         a0 = !dup;
                     }
-                    if (a1 && P.skip < 2) {
+                    if (a1 && !P.keep_dups) {
                         bool dup;
                         const uint32_t r2 = r1 + 1u;
                         if (r2 < nt) {
@@ -1328,22 +813,19 @@ k_scan_agg_range2(AggParams P, RangeAux R) {
                         a1 = !dup;
                     }
                     my_matched += (a0 ? 1u : 0u) + (a1 ? 1u : 0u);
-                    if (P.skip == 1) continue;
                     // in-lane pair merge, then direct LDS updates
                     const bool merge = a0 && a1 && (s0 == s1);
                     if (merge) {
                         lds_update<MM>(P, lkey, lsum, lcnt, lmin, lmax, ne,
                                        s0, v0 + v1, 2u, fmin(v0, v1),
-                                       fmax(v0, v1), iA, preA, true);
+                                       fmax(v0, v1), iA, preA);
                     } else {
                         if (a0)
                             lds_update<MM>(P, lkey, lsum, lcnt, lmin, lmax,
-                                           ne, s0, v0, 1u, v0, v0, iA, preA,
-                                           true);
+                                           ne, s0, v0, 1u, v0, v0, iA, preA);
                         if (a1)
                             lds_update<MM>(P, lkey, lsum, lcnt, lmin, lmax,
-                                           ne, s1, v1, 1u, v1, v1, iB, preB,
-                                           true);
+                                           ne, s1, v1, 1u, v1, v1, iB, preB);
                     }
                 }
                 pos++;
@@ -1723,7 +1205,6 @@ k_unique_u64(const uint64_t* __restrict__ in, unsigned long long n,
 struct CompactParams {
     AggTable table;
     uint32_t n_slots;
-    uint32_t ops;
     int32_t key_claim;
     int64_t bucket_ms;
     // direct-indexed bucket mode
@@ -1740,129 +1221,11 @@ struct CompactParams {
     unsigned long long* n_out;
 };
 
-extern "C" __global__ void __launch_bounds__(256)
-k_compact(CompactParams C) {
-    const int lane = threadIdx.x & 63;
-    const uint32_t stride = blockDim.x * gridDim.x;
-    if (C.n_buckets) {  // direct-indexed bucket mode: sweep (slot, bucket)
-        const size_t total = (size_t)C.n_slots * C.n_buckets;
-        for (size_t p = blockIdx.x * blockDim.x + threadIdx.x;
-             __any(p < total); p += stride) {
-            bool live = false;
-            uint64_t key = 0;
-            const uint8_t* brow = nullptr;
-            if (p < total) {
-                const uint32_t slot_i = (uint32_t)(p / C.n_buckets);
-                key = *(const uint64_t*)(C.table.slab +
-                                         (size_t)slot_i * C.table.stride);
-                brow = C.bstore + p * C.bstride;
-                live = key != KEY_EMPTY &&
-                       *(const unsigned long long*)(brow + 8) > 0;
-            }
-            const unsigned long long mask = __ballot(live);
-            if (!mask) continue;
-            const int leader = __ffsll((unsigned long long)mask) - 1;
-            unsigned long long wave_base = 0;
-            if (lane == leader)
-                wave_base =
-                    atomicAdd(C.n_out, (unsigned long long)__popcll(mask));
-            wave_base = __shfl(wave_base, leader, 64);
-            if (live) {
-                const unsigned long long j =
-                    wave_base + __popcll(mask & ((1ull << lane) - 1ull));
-                C.out_series[j] = key;
-                C.out_bucket[j] =
-                    C.lo_bucket + (long long)(p % C.n_buckets);
-                if (C.out_sum) C.out_sum[j] = *(const double*)brow;
-                if (C.out_cnt)
-                    C.out_cnt[j] = *(const unsigned long long*)(brow + 8);
-                if (C.out_min)
-                    C.out_min[j] = ordered_f64(
-                        *(const unsigned long long*)(brow + 16));
-                if (C.out_max)
-                    C.out_max[j] = ordered_f64(
-                        *(const unsigned long long*)(brow + 24));
-            }
-        }
-        return;
-    }
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-         __any(i < C.n_slots); i += stride) {
-        const uint8_t* slot = C.table.slab + (size_t)i * C.table.stride;
-        const bool live = (i < C.n_slots) &&
-                          (C.key_claim ? (*(const uint64_t*)slot != KEY_EMPTY)
-                                       : (*(const uint32_t*)slot == 2u));
-        const unsigned long long mask = __ballot(live);
-        if (!mask) continue;
-        // one atomic per wave (guideline 12): first live lane reserves
-        const int leader = __ffsll((unsigned long long)mask) - 1;
-        unsigned long long wave_base = 0;
-        if (lane == leader)
-            wave_base = atomicAdd(C.n_out, (unsigned long long)__popcll(mask));
-        wave_base = __shfl(wave_base, leader, 64);
-        if (live) {
-            const unsigned long long j =
-                wave_base + __popcll(mask & ((1ull << lane) - 1ull));
-            if (C.key_claim && C.table.rep) {
-                C.out_series[j] = *(const uint64_t*)slot;
-                double sum = 0, mnv = HUGE_VAL, mxv = -HUGE_VAL;
-                unsigned long long cntv = 0;
-                for (uint32_t x = 0; x < 8; x++) {
-                    const uint8_t* r2 =
-                        C.table.rep +
-                        ((size_t)x * (C.table.mask + 1ull) + i) *
-                            C.table.rep_stride;
-                    sum += *(const double*)r2;
-                    cntv += *(const unsigned long long*)(r2 + 8);
-                    if (C.out_min)
-                        mnv = fmin(mnv, ordered_f64(
-                                            *(const unsigned long long*)(r2 + 16)));
-                    if (C.out_max)
-                        mxv = fmax(mxv, ordered_f64(
-                                            *(const unsigned long long*)(r2 + 24)));
-                }
-                if (C.out_sum) C.out_sum[j] = sum;
-                if (C.out_cnt) C.out_cnt[j] = cntv;
-                if (C.out_min) C.out_min[j] = mnv;
-                if (C.out_max) C.out_max[j] = mxv;
-            } else if (C.key_claim) {
-                C.out_series[j] = *(const uint64_t*)slot;
-                if (C.out_sum) C.out_sum[j] = *(const double*)(slot + 8);
-                if (C.out_cnt)
-                    C.out_cnt[j] = *(const unsigned long long*)(slot + 16);
-                if (C.out_min)
-                    C.out_min[j] = ordered_f64(
-                        *(const unsigned long long*)(slot + 24));
-                if (C.out_max)
-                    C.out_max[j] = ordered_f64(
-                        *(const unsigned long long*)(slot + 32));
-            } else {
-                C.out_series[j] = *(const uint64_t*)(slot + 8);
-                if (C.bucket_ms)
-                    C.out_bucket[j] = *(const long long*)(slot + 16);
-                if (C.out_sum) C.out_sum[j] = *(const double*)(slot + 24);
-                if (C.out_cnt)
-                    C.out_cnt[j] = *(const unsigned long long*)(slot + 32);
-                if (C.out_min)
-                    C.out_min[j] = ordered_f64(
-                        *(const unsigned long long*)(slot + 40));
-                if (C.out_max)
-                    C.out_max[j] = ordered_f64(
-                        *(const unsigned long long*)(slot + 48));
-            }
-        }
-    }
+// Sweep positions: one per slot, or (direct-indexed bucket mode) one per
+// (slot, bucket) accumulator row.
+__device__ __forceinline__ size_t compact_total(const CompactParams& C) {
+    return C.n_buckets ? (size_t)C.n_slots * C.n_buckets : (size_t)C.n_slots;
 }
-
-// ---- two-phase compaction (non-bucket slab/state tables) ------------------
-// The single-pass k_compact reserves output positions with one agent-scope
-// atomicAdd per live wave on ONE counter word. At headline fill (10M live in
-// a 16M-slot table) that is ~250k serialized hot-word RMWs ≈ 2.8 ms — the
-// same coherence-point storm the scan kernel's fill counter had (§9c). The
-// two-phase form removes the hot word entirely: per-block live counts
-// (no atomics), a one-block exclusive scan, then an atomic-free write pass
-// positioned by block base + LDS-local offset. Sweep traffic is paid twice
-// but is only ~0.5 GB at headline size.
 
 __device__ __forceinline__ bool compact_live(const CompactParams& C,
                                              size_t p) {
@@ -1878,76 +1241,71 @@ __device__ __forceinline__ bool compact_live(const CompactParams& C,
                        : (*(const uint32_t*)slot == 2u);
 }
 
+// Write live position p as output group j.
 __device__ __forceinline__ void compact_emit(const CompactParams& C,
                                              size_t p,
                                              unsigned long long j) {
+    const uint8_t* acc;   // {sum, cnt[, min, max]} of this group
     if (C.n_buckets) {
         const uint32_t slot_i = (uint32_t)(p / C.n_buckets);
-        const uint8_t* brow = C.bstore + p * C.bstride;
         C.out_series[j] = *(const uint64_t*)(
             C.table.slab + (size_t)slot_i * C.table.stride);
         C.out_bucket[j] = C.lo_bucket + (long long)(p % C.n_buckets);
-        if (C.out_sum) C.out_sum[j] = *(const double*)brow;
-        if (C.out_cnt)
-            C.out_cnt[j] = *(const unsigned long long*)(brow + 8);
-        if (C.out_min)
-            C.out_min[j] =
-                ordered_f64(*(const unsigned long long*)(brow + 16));
-        if (C.out_max)
-            C.out_max[j] =
-                ordered_f64(*(const unsigned long long*)(brow + 24));
-        return;
-    }
-    const uint32_t i = (uint32_t)p;
-    const uint8_t* slot = C.table.slab + (size_t)i * C.table.stride;
-    if (C.key_claim && C.table.rep) {
-        C.out_series[j] = *(const uint64_t*)slot;
-        double sum = 0, mnv = HUGE_VAL, mxv = -HUGE_VAL;
-        unsigned long long cntv = 0;
-        for (uint32_t x = 0; x < 8; x++) {
-            const uint8_t* r2 =
-                C.table.rep +
-                ((size_t)x * (C.table.mask + 1ull) + i) * C.table.rep_stride;
-            sum += *(const double*)r2;
-            cntv += *(const unsigned long long*)(r2 + 8);
-            if (C.out_min)
-                mnv = fmin(mnv,
-                           ordered_f64(*(const unsigned long long*)(r2 + 16)));
-            if (C.out_max)
-                mxv = fmax(mxv,
-                           ordered_f64(*(const unsigned long long*)(r2 + 24)));
-        }
-        if (C.out_sum) C.out_sum[j] = sum;
-        if (C.out_cnt) C.out_cnt[j] = cntv;
-        if (C.out_min) C.out_min[j] = mnv;
-        if (C.out_max) C.out_max[j] = mxv;
-    } else if (C.key_claim) {
-        C.out_series[j] = *(const uint64_t*)slot;
-        if (C.out_sum) C.out_sum[j] = *(const double*)(slot + 8);
-        if (C.out_cnt) C.out_cnt[j] = *(const unsigned long long*)(slot + 16);
-        if (C.out_min)
-            C.out_min[j] =
-                ordered_f64(*(const unsigned long long*)(slot + 24));
-        if (C.out_max)
-            C.out_max[j] =
-                ordered_f64(*(const unsigned long long*)(slot + 32));
+        acc = C.bstore + p * C.bstride;
     } else {
-        C.out_series[j] = *(const uint64_t*)(slot + 8);
-        if (C.bucket_ms) C.out_bucket[j] = *(const long long*)(slot + 16);
-        if (C.out_sum) C.out_sum[j] = *(const double*)(slot + 24);
-        if (C.out_cnt) C.out_cnt[j] = *(const unsigned long long*)(slot + 32);
-        if (C.out_min)
-            C.out_min[j] =
-                ordered_f64(*(const unsigned long long*)(slot + 40));
-        if (C.out_max)
-            C.out_max[j] =
-                ordered_f64(*(const unsigned long long*)(slot + 48));
+        const uint8_t* slot = C.table.slab + p * C.table.stride;
+        if (C.key_claim) {   // {key, sum, ...}
+            C.out_series[j] = *(const uint64_t*)slot;
+            acc = slot + 8;
+        } else {   // {state, pad, series, bucket, sum, ...}
+            C.out_series[j] = *(const uint64_t*)(slot + 8);
+            if (C.bucket_ms) C.out_bucket[j] = *(const long long*)(slot + 16);
+            acc = slot + 24;
+        }
+    }
+    if (C.out_sum) C.out_sum[j] = *(const double*)acc;
+    if (C.out_cnt) C.out_cnt[j] = *(const unsigned long long*)(acc + 8);
+    if (C.out_min)
+        C.out_min[j] = ordered_f64(*(const unsigned long long*)(acc + 16));
+    if (C.out_max)
+        C.out_max[j] = ordered_f64(*(const unsigned long long*)(acc + 24));
+}
+
+// Single-pass compaction: output positions reserved with one atomicAdd on
+// n_out per live wave. The route for direct-indexed bucket tables, whose
+// sweep walks slots x n_buckets positions at a low live fraction: few live
+// waves, so few atomics, and sweeping twice measured slower.
+extern "C" __global__ void __launch_bounds__(256)
+k_compact(CompactParams C) {
+    const int lane = threadIdx.x & 63;
+    const size_t total = compact_total(C);
+    const size_t stride = (size_t)blockDim.x * gridDim.x;
+    for (size_t p = blockIdx.x * blockDim.x + threadIdx.x; __any(p < total);
+         p += stride) {
+        const bool live = p < total && compact_live(C, p);
+        const unsigned long long mask = __ballot(live);
+        if (!mask) continue;
+        // first live lane reserves for the wave
+        const int leader = __ffsll(mask) - 1;
+        unsigned long long wave_base = 0;
+        if (lane == leader)
+            wave_base = atomicAdd(C.n_out, (unsigned long long)__popcll(mask));
+        wave_base = __shfl(wave_base, leader, 64);
+        if (live)
+            compact_emit(C, p,
+                         wave_base + __popcll(mask & ((1ull << lane) - 1ull)));
     }
 }
 
-__device__ __forceinline__ size_t compact_total(const CompactParams& C) {
-    return C.n_buckets ? (size_t)C.n_slots * C.n_buckets : (size_t)C.n_slots;
-}
+// ---- two-phase compaction (non-bucket slab/state tables) ------------------
+// k_compact reserves output positions with one agent-scope atomicAdd per
+// live wave on ONE counter word. At headline fill (10M live in a 16M-slot
+// table) that is ~250k serialized hot-word RMWs ≈ 2.8 ms — the same
+// coherence-point storm the scan kernel's fill counter had (§9c). The
+// two-phase form removes the hot word entirely: per-block live counts
+// (no atomics), a one-block exclusive scan, then an atomic-free write pass
+// positioned by block base + LDS-local offset. Sweep traffic is paid twice
+// but is only ~0.5 GB at headline size.
 
 extern "C" __global__ void __launch_bounds__(256)
 k_compact_count(CompactParams C, uint32_t* __restrict__ counts) {
@@ -3058,48 +2416,6 @@ hipError_t launch_scan_agg(hipStream_t s, const AggParams& p, uint32_t grid) {
     return hipGetLastError();
 }
 
-hipError_t launch_scan_agg_gang(hipStream_t s, const AggParams& p,
-                                uint32_t gang_size, bool minmax,
-                                GangParams* h_params, GangParams* d_params) {
-    GangParams& G = *h_params;
-    G.P = p;
-    G.gang_size = gang_size;
-    G.n_gangs = (p.n_rgs + gang_size - 1) / gang_size;
-    G.has_mm = minmax ? 1u : 0u;
-    // LDS table holds the distinct keys of one aligned unit window (host
-    // slices units to <= ne/2 distinct); 4096 x 20B = 80 KiB => 2 blocks
-    // (32 waves) per CU for latency hiding.
-    G.ne = minmax ? 2048u : 4096u;
-    if (const char* nee = getenv("HX_NE")) {
-        uint32_t ne = (uint32_t)strtoul(nee, nullptr, 10);
-        if (ne >= 1024 && ne <= 8192 && !(ne & (ne - 1))) G.ne = ne;
-    }
-    size_t lds = 320 + (size_t)G.ne * (minmax ? 36 : 20) +
-                 (size_t)G.gang_size * sizeof(RgDesc);
-    uint32_t grid = G.n_gangs > 4096 ? 4096 : (G.n_gangs ? G.n_gangs : 1);
-    // >64 KiB dynamic LDS needs an explicit opt-in per kernel
-    static bool lds_opted[2] = {false, false};
-    if (!lds_opted[minmax ? 1 : 0]) {
-        const void* f = minmax
-            ? reinterpret_cast<const void*>(&k_scan_agg_gang<true>)
-            : reinterpret_cast<const void*>(&k_scan_agg_gang<false>);
-        hipError_t ae = hipFuncSetAttribute(
-            f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (ae != hipSuccess) return ae;
-        lds_opted[minmax ? 1 : 0] = true;
-    }
-    hipError_t e = hipMemcpyAsync(d_params, h_params, sizeof(GangParams),
-                                  hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) return e;
-    if (minmax)
-        hipLaunchKernelGGL(k_scan_agg_gang<true>, dim3(grid), dim3(1024), lds,
-                           s, d_params, p.blob, p.dec, p.rgs);
-    else
-        hipLaunchKernelGGL(k_scan_agg_gang<false>, dim3(grid), dim3(1024), lds,
-                           s, d_params, p.blob, p.dec, p.rgs);
-    return hipGetLastError();
-}
-
 hipError_t launch_sample_series(hipStream_t s, const RgDesc* rgs,
                                 uint32_t n_rgs, const uint8_t* blob,
                                 const uint8_t* dec, uint64_t* out) {
@@ -3143,42 +2459,6 @@ hipError_t launch_scan_agg_range2(hipStream_t s, const AggParams& p,
     return hipGetLastError();
 }
 
-hipError_t launch_scan_agg_range(hipStream_t s, const AggParams& p,
-                                 const RangeAux& r, bool minmax) {
-    const size_t lds = (size_t)r.ne * (minmax ? 36 : 20);
-    // occupancy: the unconstrained build allocates 118 VGPRs => 4 waves/
-    // SIMD (16/CU). MINW 5/6 force the register budget down (<=96/<=80)
-    // at 80/128 B of spill; after the fill-counter fix all three measure
-    // within ~3% (7.1-7.4 ms) — default 1 (no spill) keeps the PMC
-    // traffic at the algorithmic 1.1-1.3x instead of +7 GB of scratch.
-    int minw = 1;
-    if (const char* e = getenv("HX_MINW")) minw = atoi(e);
-    const void* f;
-    if (minmax)
-        f = minw >= 6 ? (const void*)&k_scan_agg_range<true, 6>
-            : minw == 5 ? (const void*)&k_scan_agg_range<true, 5>
-                        : (const void*)&k_scan_agg_range<true, 1>;
-    else
-        f = minw >= 6 ? (const void*)&k_scan_agg_range<false, 6>
-            : minw == 5 ? (const void*)&k_scan_agg_range<false, 5>
-                        : (const void*)&k_scan_agg_range<false, 1>;
-    // >64 KiB dynamic LDS requires the opt-in or the launch FAILS silently
-    // (measured the hard way on the gang kernel). Request only what this
-    // launch needs: the kernel's static shared (s_abort) counts against
-    // the 160 KiB block limit, so asking for the full 160 KiB is itself
-    // an invalid argument.
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(
-            f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(
-        reinterpret_cast<void (*)(AggParams, RangeAux)>(
-            const_cast<void*>(f)),
-        dim3(r.n_blocks), dim3(256), lds, s, p, r);
-    return hipGetLastError();
-}
-
 hipError_t launch_scan_rows(hipStream_t s, const AggParams& p,
                             uint32_t rg_first, uint32_t rg_last,
                             uint64_t* out_series, long long* out_ts,
@@ -3218,14 +2498,13 @@ hipError_t launch_gather_multi(hipStream_t s,
 }
 
 hipError_t launch_compact(hipStream_t s, const AggTable& t, uint32_t n_slots,
-                          uint32_t ops, int32_t key_claim, int64_t bucket_ms,
+                          int32_t key_claim, int64_t bucket_ms,
                           int64_t lo_bucket, uint32_t n_buckets,
                           uint32_t bstride, const uint8_t* bstore,
                           const CompactOut& o, uint32_t* scratch) {
     CompactParams C;
     C.table = t;
     C.n_slots = n_slots;
-    C.ops = ops;
     C.key_claim = key_claim;
     C.bucket_ms = bucket_ms;
     C.lo_bucket = lo_bucket;
@@ -3252,11 +2531,7 @@ hipError_t launch_compact(hipStream_t s, const AggTable& t, uint32_t n_slots,
     // and doubling that sweep measured ~5% SLOWER than the single-pass
     // kernel's atomics (201.8 vs 192.9 ms/step same-box) — the storm is
     // proportional to LIVE waves, which bucket sweeps have few of.
-    static const bool legacy = [] {
-        const char* e = getenv("HX_COMPACT_LEGACY");
-        return e && atoi(e) != 0;
-    }();
-    if (n_buckets == 0 && scratch && !legacy) {
+    if (n_buckets == 0) {
         uint32_t* counts = scratch;
         uint32_t* bases = scratch + grid;
         hipLaunchKernelGGL(k_compact_count, dim3(grid), dim3(256), 0, s,
@@ -3319,12 +2594,13 @@ hipError_t launch_init_state_slab(hipStream_t s, uint8_t* slab,
     return hipGetLastError();
 }
 
-hipError_t launch_init_rep(hipStream_t s, uint8_t* rep, size_t total_slots,
-                           uint32_t stride, bool mm) {
-    hipLaunchKernelGGL(k_init_rep,
+hipError_t launch_init_accum_rows(hipStream_t s, uint8_t* rows,
+                                  size_t total_rows, uint32_t stride,
+                                  bool mm) {
+    hipLaunchKernelGGL(k_init_accum_rows,
                        dim3(grid_for((uint32_t)std::min<size_t>(
-                                         total_slots, 0x7FFFFFFF), 256)),
-                       dim3(256), 0, s, rep, total_slots, stride,
+                                         total_rows, 0x7FFFFFFF), 256)),
+                       dim3(256), 0, s, rows, total_rows, stride,
                        mm ? 1u : 0u);
     return hipGetLastError();
 }

@@ -607,6 +607,41 @@ def test_wave_kernel_fallback_parity(ds_plain):
         del os.environ["HX_RANGE"]
 
 
+def test_state_word_path_parity(tmp_path):
+    # a series id equal to the key-claim sentinel (2**64 - 1) makes the store
+    # unsafe for one-CAS key claims, so BOTH queries run on the state-word
+    # table ({state, series, bucket, ...} slots): series-only grouping through
+    # the two-phase compaction, and (series, bucket) hashing with bucket_ms > 0
+    # (the direct-indexed bucket store needs key claims too)
+    store = str(tmp_path)
+    rng = np.random.default_rng(21)
+    ids = rng.integers(1, 2**63, 300).astype(np.uint64)
+    ids[0] = np.uint64(2**64 - 1)
+    for seq in (1, 2):
+        n = 20_000
+        series = ids[rng.integers(0, 300, n)]
+        ts = rng.integers(0, 400, n).astype(np.int64) * 10
+        gen_sst_from_arrays(store, seq, series, ts, rng.random(n))
+    res = check_parity(store, (0, 10**6), ops=OPS_ALL, bucket_ms=0)
+    assert len(res["series_id"]) == 300
+    assert int(res["series_id"][-1]) == 2**64 - 1
+    res = check_parity(store, (0, 10**6), ops=OPS_ALL, bucket_ms=250)
+    assert len(res["series_id"]) > 300   # more than one bucket per series
+    assert int(res["series_id"].max()) == 2**64 - 1
+
+
+def test_force_state_switch_parity(ds_plain):
+    # HX_FORCE_STATE=1 routes a key-claim-safe store through the state-word
+    # table (bucketed and series-only) with identical results
+    out, m = ds_plain
+    os.environ["HX_FORCE_STATE"] = "1"
+    try:
+        check_parity(out, middle_range(m), ops=OPS_ALL, bucket_ms=60_000)
+        check_parity(out, middle_range(m), ops=OPS_ALL, bucket_ms=0)
+    finally:
+        del os.environ["HX_FORCE_STATE"]
+
+
 def test_invalid_agg_args(ds_plain):
     # argument validation surfaces HX_ERR_INVALID, not kernel misbehavior
     from horaedb_amd import Store, HxError
