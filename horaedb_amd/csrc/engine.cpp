@@ -412,6 +412,8 @@ struct DevPlan {
     uint32_t range_nblocks = 0;
     double range_xest = 0;   // distinct-series estimate (sizes the table)
     bool range_ready = false;
+    uint64_t sorted_cap = 0;       // sorted-run staging capacity that fit
+    bool sorted_gave_up = false;   // retries ran out once: global-table route
 
     hipStream_t stream = nullptr;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // timing
@@ -1466,7 +1468,12 @@ static hx::AggParams base_params(hx_prepared* P, DevPlan& plan) {
 // inverted by bisection) -> equal-sample quantile boundaries -> cached
 // per-(block, sst) row bounds via k_range_bounds. Decode is deterministic,
 // so the cached row bounds stay valid under HX_REDECODE.
-static hx_status ensure_range(DevPlan& plan, const hx::AggParams& base) {
+// min_nb > 0 (a retry after an LDS block overflow) forces at least that many
+// blocks and interpolates the boundaries between adjacent samples, so the
+// split keeps refining where there are fewer samples than blocks.
+static hx_status ensure_range(DevPlan& plan, const hx::AggParams& base,
+                              uint32_t min_nb = 0) {
+    plan.range_ready = false;
     const uint32_t n_rgs = (uint32_t)plan.rgs.size();
     const uint32_t n_ssts = (uint32_t)plan.ssts.size();
     if (!n_rgs || !n_ssts) return HX_OK;  // leaves range_ready false
@@ -1518,9 +1525,21 @@ static hx_status ensure_range(DevPlan& plan, const hx::AggParams& base) {
     // storm (r01: 286M of 320M updates went global at the 1B shape).
     if (!getenv("HX_RANGE_TARGET"))   // explicit target: trust the caller
         while ((double)nb * 32768.0 < staged && nb < (1u << 17)) nb <<= 1;
+    while (nb < min_nb && nb < (1u << 17)) nb <<= 1;
+    if (nb < min_nb) return HX_OK;   // cannot split further: not ready
     std::vector<uint64_t> bounds(nb + 1);
     bounds[0] = 0;
-    for (uint32_t b = 1; b < nb; b++) bounds[b] = samp[(size_t)b * m / nb];
+    for (uint32_t b = 1; b < nb; b++) {
+        if (!min_nb) {
+            bounds[b] = samp[(size_t)b * m / nb];
+            continue;
+        }
+        const double pos = (double)b * (double)m / (double)nb;
+        const size_t i = std::min((size_t)pos, m - 1);
+        const uint64_t lo = samp[i], hi = samp[std::min(i + 1, m - 1)];
+        const uint64_t v = lo + (uint64_t)((double)(hi - lo) * (pos - (double)i));
+        bounds[b] = std::max(bounds[b - 1], std::min(v, hi));
+    }
     bounds[nb] = ~0ull;
     if (plan.d_range_bounds) { hipFree(plan.d_range_bounds); plan.d_range_bounds = nullptr; }
     if (plan.d_bound_rows) { hipFree(plan.d_bound_rows); plan.d_bound_rows = nullptr; }
@@ -1539,6 +1558,186 @@ static hx_status ensure_range(DevPlan& plan, const hx::AggParams& base) {
     HIP_TRY(hipStreamSynchronize(s));
     plan.range_nblocks = nb;
     plan.range_ready = true;
+    return HX_OK;
+}
+
+// Series-only grouping on the range path: the range kernel emits
+// each block's groups as one key-ordered run, two small kernels place the
+// runs in block order into the contiguous SoA result, and the host syncs
+// once to read the counters before the single D2H. No global table, no
+// compaction, no sort. Both overflows are retried exactly: a full staging
+// area with the capacity the cursor reported, a block that met more than ne
+// keys with twice the blocks. *done stays false when the attempts run out;
+// the caller then takes the global-table route.
+static hx_status exec_range_sorted(hx_prepared* P, DevPlan& plan,
+                                   const hx_agg_spec* agg, uint32_t ops,
+                                   HostTable& out, double* agg_kernel_ms,
+                                   unsigned long long* matched_out,
+                                   bool* done) {
+    hipStream_t s = plan.stream;
+    const bool mm = (ops & (HX_AGG_MIN | HX_AGG_MAX)) != 0;
+    const bool has_sum = (ops & (HX_AGG_SUM | HX_AGG_AVG)) != 0;
+    const bool has_cnt = (ops & (HX_AGG_COUNT | HX_AGG_AVG)) != 0;
+    const bool has_min = (ops & HX_AGG_MIN) != 0;
+    const bool has_max = (ops & HX_AGG_MAX) != 0;
+    const bool has_avg = (agg->ops & HX_AGG_AVG) != 0;
+    int32_t na = 1;
+    const int32_t c_sum = has_sum ? na++ : -1;
+    const int32_t c_cnt = has_cnt ? na++ : -1;
+    const int32_t c_min = has_min ? na++ : -1;
+    const int32_t c_max = has_max ? na++ : -1;
+    const int32_t c_avg = has_avg ? na++ : -1;
+    const uint32_t n_total = (uint32_t)na;
+    const uint32_t n_stage = mm ? 5 : 3;
+
+    uint64_t staged = 0;
+    for (const auto& sd : plan.ssts) staged += (uint64_t)sd.n_staged;
+    uint64_t cap = plan.sorted_cap;
+    if (!cap) {
+        // the estimate that sizes the global table; never more than one
+        // group per staged row
+        if (const char* env = getenv("HX_TABLE_SLOTS"))
+            cap = next_pow2_u32(strtoull(env, nullptr, 10));
+        else
+            cap = std::max<uint64_t>(
+                std::max<uint64_t>(1 << 16, (uint64_t)plan.rows_scanned / 32),
+                (uint64_t)(plan.range_xest * 1.4));
+        cap = std::min(cap, std::max<uint64_t>(staged, 1));
+    }
+    unsigned long long counters[6];
+    for (int attempt = 0; attempt < 4; attempt++) {
+        if (cap > 0xFFFFFFFFull)
+            return fail(HX_ERR_UNSUPPORTED, "result exceeds 2^32 groups");
+        const uint32_t nb = plan.range_nblocks;
+        uint32_t ne = 1024;
+        if (const char* e = getenv("HX_RANGE_NE"))
+            ne = (uint32_t)strtoul(e, nullptr, 10);
+        const size_t need = size_t(cap) * 8 * (n_stage + n_total) +
+                            size_t(nb) * 12 + 256;
+        hx_status st = ensure_dev(&plan.d_scratch, &plan.scratch_cap, need);
+        if (st != HX_OK) return st;
+        uint8_t* base = (uint8_t*)plan.d_scratch;
+        auto carve8 = [&](size_t count) {
+            uint8_t* p = base;
+            base += count * 8;
+            return p;
+        };
+        hx::RangeOut O{};
+        O.key = (uint64_t*)carve8(cap);
+        O.sum = (double*)carve8(cap);
+        O.cnt = (unsigned long long*)carve8(cap);
+        O.vmin = mm ? (double*)carve8(cap) : nullptr;
+        O.vmax = mm ? (double*)carve8(cap) : nullptr;
+        unsigned long long* d_dst =
+            (unsigned long long*)carve8(size_t(cap) * n_total);
+        O.desc = (uint64_t*)carve8(nb);
+        uint32_t* d_prefix = (uint32_t*)base;
+        O.cap = cap;
+        O.cursor = plan.d_counters + 0;
+        O.stage_ovf = plan.d_counters + 1;
+        O.block_ovf = plan.d_counters + 4;
+        HIP_TRY(hipMemsetAsync(plan.d_counters, 0, 48, s));
+
+        hx::AggParams A = base_params(P, plan);
+        A.ops = ops;
+        A.key_claim = 1;
+        A.fill = plan.d_counters + 0;
+        A.overflow = plan.d_counters + 1;
+        A.matched = plan.d_counters + 2;
+        hx::RangeAux R{plan.d_range_bounds, plan.d_bound_rows,
+                       plan.d_sst_rgs,     plan.d_sst_rg_off,
+                       plan.d_sst_rg_cnt,  (uint32_t)plan.ssts.size(),
+                       nb,                 ne};
+        hx::RangePlace Q{};
+        Q.desc = O.desc;
+        Q.prefix = d_prefix;
+        Q.n_blocks = nb;
+        Q.key = O.key;
+        Q.sum = O.sum;
+        Q.cnt = O.cnt;
+        Q.vmin = O.vmin;
+        Q.vmax = O.vmax;
+        Q.dst = d_dst;
+        Q.c_sum = c_sum;
+        Q.c_cnt = c_cnt;
+        Q.c_min = c_min;
+        Q.c_max = c_max;
+        Q.c_avg = c_avg;
+        Q.cap = cap;
+        Q.cursor = O.cursor;
+        Q.stage_ovf = O.stage_ovf;
+        Q.block_ovf = O.block_ovf;
+
+        hx_status est = ensure_events(plan);
+        if (est != HX_OK) return est;
+        hipEvent_t e0 = plan.ev[0], e1 = plan.ev[1];
+        HIP_TRY(hipEventRecord(e0, s));
+        hipError_t ke = hx::launch_scan_agg_range2(s, A, R, mm, &O);
+        if (ke != hipSuccess)
+            return fail(HX_ERR_HIP,
+                        std::string("range kernel launch failed: ") +
+                            hipGetErrorString(ke));
+        HIP_TRY(hipEventRecord(e1, s));
+        ke = hx::launch_place_runs(s, Q);
+        if (ke != hipSuccess)
+            return fail(HX_ERR_HIP,
+                        std::string("run placement launch failed: ") +
+                            hipGetErrorString(ke));
+        HIP_TRY(hipStreamSynchronize(s));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+        HIP_TRY(hipMemcpy(counters, plan.d_counters, 48,
+                          hipMemcpyDeviceToHost));
+        if (getenv("HX_DEBUG"))
+            fprintf(stderr,
+                    "[hx] exec attempt=%d kernel=range-sorted cap=%llu nb=%u "
+                    "ne=%u xest=%.0f kernel_ms=%.2f groups=%llu "
+                    "stage_overflow=%llu block_overflow=%llu matched=%llu\n",
+                    attempt, (unsigned long long)cap, nb, ne, plan.range_xest,
+                    ms, counters[0], counters[1], counters[4], counters[2]);
+        if (counters[4]) {   // > ne keys in one block: halve the ranges
+            if (attempt == 3) break;
+            hx::AggParams rb{};
+            rb.rgs = plan.d_rgs;
+            rb.blob = plan.d_blob;
+            rb.dec = plan.d_dec;
+            hx_status rs = ensure_range(plan, rb, nb * 2);
+            if (rs != HX_OK) return rs;
+            if (!plan.range_ready) break;
+            continue;
+        }
+        const unsigned long long total = counters[0];
+        if (counters[1] || total > cap) {   // staging full: total is exact
+            if (attempt == 3) break;
+            cap = total;
+            continue;
+        }
+        plan.sorted_cap = cap;
+        *agg_kernel_ms = ms;
+        *matched_out = counters[2];
+        *done = true;
+        out.release();
+        out.n = total;
+        if (total == 0) return HX_OK;
+        const size_t ng = (size_t)total;
+        const size_t bytes = ng * 8 * n_total;
+        out.buf = g_result_pool.acquire(bytes, &out.pinned, &out.cap);
+        if (!out.buf) return fail(HX_ERR_IO, "result alloc failed");
+        HIP_TRY(hipMemcpyAsync(out.buf, d_dst, bytes, hipMemcpyDeviceToHost,
+                               s));
+        HIP_TRY(hipStreamSynchronize(s));
+        uint64_t* hb = (uint64_t*)out.buf;
+        out.series = hb;
+        out.bucket = nullptr;
+        out.sum = has_sum ? (double*)(hb + size_t(c_sum) * ng) : nullptr;
+        out.cnt = has_cnt ? (unsigned long long*)(hb + size_t(c_cnt) * ng)
+                          : nullptr;
+        out.vmin = has_min ? (double*)(hb + size_t(c_min) * ng) : nullptr;
+        out.vmax = has_max ? (double*)(hb + size_t(c_max) * ng) : nullptr;
+        out.avg = has_avg ? (double*)(hb + size_t(c_avg) * ng) : nullptr;
+        return HX_OK;
+    }
+    plan.sorted_gave_up = true;
     return HX_OK;
 }
 
@@ -1624,6 +1823,20 @@ hx_status exec_plan(hx_prepared* P, DevPlan& plan, const hx_agg_spec* agg,
         if (rs != HX_OK) return rs;
     }
     if (use_range && !plan.range_ready) use_range = false;
+
+    // sorted-run result path. HX_RANGE_SORTED=0 keeps the range
+    // kernel's flush into the global table for A/B runs.
+    bool sorted = use_range && !plan.sorted_gave_up;
+    if (const char* senv = getenv("HX_RANGE_SORTED"))
+        sorted = sorted && atoi(senv) != 0;
+    if (sorted) {
+        bool done = false;
+        hx_status rs = exec_range_sorted(P, plan, agg, ops, out,
+                                         agg_kernel_ms, matched_out, &done);
+        if (rs != HX_OK || done) return rs;
+    }
+    // a block range that will not fit LDS: the wave kernel has no such limit
+    if (plan.sorted_gave_up) use_range = false;
 
     // table size heuristic; grows on overflow
     uint32_t slots = plan.slots;
@@ -1713,7 +1926,7 @@ hx_status exec_plan(hx_prepared* P, DevPlan& plan, const hx_agg_spec* agg,
                            plan.d_sst_rg_cnt,  (uint32_t)plan.ssts.size(),
                            plan.range_nblocks, ne};
             hipError_t re2 = hx::launch_scan_agg_range2(
-                s, A, R, (ops & (HX_AGG_MIN | HX_AGG_MAX)) != 0);
+                s, A, R, (ops & (HX_AGG_MIN | HX_AGG_MAX)) != 0, nullptr);
             if (re2 != hipSuccess)
                 return fail(HX_ERR_HIP,
                             std::string("range kernel launch failed: ") +

@@ -121,6 +121,45 @@ struct RangeAux {
     uint32_t ne;
 };
 
+// Sorted-run output of k_scan_agg_range2: block b orders its LDS
+// entries by key and writes them as one contiguous run into SoA staging at
+// an offset reserved from `cursor` (one agent-scope add per block); desc[b]
+// = count << 32 | offset. Blocks own disjoint ascending key ranges, so placing
+// the runs in blk order (RangePlace) yields the sorted result — no global
+// table, compaction or sort.
+struct RangeOut {
+    uint64_t* key;                 // staging columns, `cap` entries each
+    double* sum;
+    unsigned long long* cnt;
+    double* vmin;                  // MM instance only
+    double* vmax;
+    uint64_t* desc;                // n_blocks x (count << 32 | offset)
+    unsigned long long cap;        // staging capacity (entries, < 2^32)
+    unsigned long long* cursor;    // total entries reserved == group count
+    unsigned long long* stage_ovf; // != 0: a run did not fit `cap`
+    unsigned long long* block_ovf; // != 0: a block met more than ne keys
+};
+
+// Placement of the staged runs into the contiguous SoA result (column c of
+// the result starts at dst + c * total, total = *cursor). A column index of
+// -1 means "not requested".
+struct RangePlace {
+    const uint64_t* desc;          // count << 32 | offset
+    uint32_t* prefix;              // n_blocks exclusive prefix of the counts
+    uint32_t n_blocks;
+    const uint64_t* key;
+    const double* sum;
+    const unsigned long long* cnt;
+    const double* vmin;
+    const double* vmax;
+    unsigned long long* dst;       // column 0 = series
+    int32_t c_sum, c_cnt, c_min, c_max, c_avg;
+    unsigned long long cap;
+    const unsigned long long* cursor;
+    const unsigned long long* stage_ovf;
+    const unsigned long long* block_ovf;
+};
+
 // DELTA_BINARY_PACKED decode unit: one page -> dense i64 at dst_off (dec).
 struct DeltaPageDesc {
     uint64_t src_off;     // page payload (bit63: in dec blob, e.g. post-snappy)

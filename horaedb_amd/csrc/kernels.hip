@@ -607,7 +607,9 @@ k_range_bounds(AggParams P, RangeAux R, uint64_t* __restrict__ out) {
 //     own pair in registers (36% of adjacent rows share a series at the
 //     headline shape) and issues its 1-2 LDS updates directly.
 // Per block: reset the LDS table, scan the block's series range in every
-// SST, flush each live LDS slot to the global table once.
+// SST, then either emit the live slots as one key-ordered run (SORTED, the
+// default: DESIGN §4) or flush each to the global table once (!SORTED, the
+// HX_RANGE_SORTED=0 A/B route).
 // ---------------------------------------------------------------------------
 
 // Add one (key, partial aggregate) to the block's LDS table, first probe at
@@ -615,16 +617,23 @@ k_range_bounds(AggParams P, RangeAux R, uint64_t* __restrict__ out) {
 // so the common-case key check pays no fresh LDS round-trip on the update
 // critical path. A stale EMPTY only re-routes through the CAS (keys
 // transition EMPTY->key exactly once), never corrupts.
-template <bool MM>
-__device__ __forceinline__ void lds_update(const AggParams& P, uint64_t* lkey,
+//
+// SORTED (the sorted-run epilogue): the probe walks the WHOLE table, so a
+// key that finds no slot proves the block holds more than ne distinct keys;
+// that returns false (block overflow, the host re-partitions) and nothing
+// goes to global memory. !SORTED keeps the 16-probe limit and routes a miss
+// to the global table.
+template <bool MM, bool SORTED>
+__device__ __forceinline__ bool lds_update(const AggParams& P, uint64_t* lkey,
                                            double* lsum, unsigned int* lcnt,
                                            unsigned long long* lmin,
                                            unsigned long long* lmax,
                                            uint32_t ne, uint64_t sv, double v,
                                            uint32_t cnt, double mn, double mx,
                                            uint32_t i, uint64_t pre) {
+    const uint32_t limit = SORTED ? ne : 16u;
 #pragma unroll 1
-    for (int probes = 0; probes < 16; probes++) {
+    for (uint32_t probes = 0; probes < limit; probes++) {
         uint64_t kk = (probes == 0) ? pre : lkey[i];
         if (kk == KEY_EMPTY) {
             uint64_t old = atomicCAS(&lkey[i], KEY_EMPTY, sv);
@@ -637,10 +646,11 @@ __device__ __forceinline__ void lds_update(const AggParams& P, uint64_t* lkey,
                 atomicMin(&lmin[i], f64_ordered(mn));
                 atomicMax(&lmax[i], f64_ordered(mx));
             }
-            return;
+            return true;
         }
         i = (i + 1) & (ne - 1);
     }
+    if (SORTED) return false;
     // LDS table full: direct global update (count it — a non-trivial rate
     // here turns the kernel into a global-RMW storm; wave-aggregated so the
     // counter itself cannot serialize)
@@ -652,19 +662,97 @@ __device__ __forceinline__ void lds_update(const AggParams& P, uint64_t* lkey,
                                    (unsigned long long)__popcll(mk), RLX, AGT);
     }
     agg_update(P, sv, 0, v, cnt, mn, mx);
+    return true;
 }
 
+// Sorted-run epilogue of one block (SORTED instances): order the live LDS
+// entries by ascending unsigned key and write them as one contiguous run.
+// The slot function is order-preserving but linear probing displaces keys
+// (and wraps), so the order is established exactly: live slot indices are
+// compacted into lidx (u16, arbitrary order), padded to a power of two with
+// the index of an EMPTY slot (key ~0 sorts last; one exists whenever padding
+// is needed, since ne is itself a power of two), and bitonic-sorted by the
+// keys they point at. Output space is reserved with ONE agent-scope add per
+// block; no block ever waits on another.
 template <bool MM>
+__device__ __forceinline__ void emit_sorted_run(
+    const RangeOut& O, uint32_t blk, uint32_t ne, const uint64_t* lkey,
+    const double* lsum, const unsigned int* lcnt,
+    const unsigned long long* lmin, const unsigned long long* lmax,
+    unsigned short* lidx, uint32_t* s_live, uint32_t* s_empty,
+    unsigned long long* s_off) {
+    for (uint32_t i = threadIdx.x; i < ne; i += blockDim.x) {
+        if (lkey[i] != KEY_EMPTY)
+            lidx[atomicAdd(s_live, 1u)] = (unsigned short)i;
+        else
+            *s_empty = i;   // any empty slot will do
+    }
+    __syncthreads();
+    const uint32_t live = *s_live;
+    uint32_t m = 1;
+    while (m < live) m <<= 1;
+    if (threadIdx.x == 0) {
+        // reserve now; the add's latency hides under the sort
+        unsigned long long off = 0;
+        if (live) off = __hip_atomic_fetch_add(O.cursor,
+                                               (unsigned long long)live, RLX,
+                                               AGT);
+        const bool fits = off + live <= O.cap;
+        if (!fits) {
+            __hip_atomic_fetch_add(O.stage_ovf, 1ull, RLX, AGT);
+            off = ~0ull;
+        }
+        *s_off = off;
+        O.desc[blk] = fits ? (((uint64_t)live << 32) | (uint64_t)off) : 0ull;
+    }
+    const uint32_t pad = *s_empty;
+    for (uint32_t p = live + threadIdx.x; p < m; p += blockDim.x)
+        lidx[p] = (unsigned short)pad;
+    __syncthreads();
+    for (uint32_t k = 2; k <= m; k <<= 1) {
+        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+            for (uint32_t t = threadIdx.x; t < (m >> 1); t += blockDim.x) {
+                const uint32_t lo = 2u * t - (t & (j - 1u));   // bit j clear
+                const uint32_t hi = lo + j;
+                const unsigned short a = lidx[lo], b = lidx[hi];
+                const bool up = (lo & k) == 0;
+                if ((lkey[a] > lkey[b]) == up) {
+                    lidx[lo] = b;
+                    lidx[hi] = a;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    const unsigned long long off = *s_off;
+    if (off == ~0ull) return;   // staging full: host retries larger
+    for (uint32_t t = threadIdx.x; t < live; t += blockDim.x) {
+        const uint32_t a = lidx[t];
+        O.key[off + t] = lkey[a];
+        O.sum[off + t] = lsum[a];
+        O.cnt[off + t] = (unsigned long long)lcnt[a];
+        if (MM) {
+            O.vmin[off + t] = ordered_f64(lmin[a]);
+            O.vmax[off + t] = ordered_f64(lmax[a]);
+        }
+    }
+}
+
+template <bool MM, bool SORTED>
 __global__ void __launch_bounds__(256)
-k_scan_agg_range2(AggParams P, RangeAux R) {
+k_scan_agg_range2(AggParams P, RangeAux R, RangeOut O) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ int s_abort;
+    __shared__ uint32_t s_live, s_empty, s_bovf;
+    __shared__ unsigned long long s_off;
     const uint32_t ne = R.ne;
     uint64_t* lkey = (uint64_t*)smem;
     double* lsum = (double*)(smem + (size_t)ne * 8);
     unsigned long long* lmin = (unsigned long long*)(smem + (size_t)ne * 16);
     unsigned long long* lmax = (unsigned long long*)(smem + (size_t)ne * 24);
     unsigned int* lcnt = (unsigned int*)(smem + (size_t)ne * (MM ? 32 : 16));
+    unsigned short* lidx =   // SORTED only: sort permutation, 2 B per slot
+        (unsigned short*)(smem + (size_t)ne * (MM ? 36 : 20));
     const int lane = threadIdx.x & 63;
     const uint32_t wave = threadIdx.x >> 6;
     const uint32_t n_waves = blockDim.x >> 6;
@@ -676,7 +764,15 @@ k_scan_agg_range2(AggParams P, RangeAux R) {
         // single-word) — polling per (wave, sst) serialized the whole kernel
         // (+23 ms at the 1B shape). A stale read only delays the abort; the
         // probe cap still bounds a doomed pass.
-        if (threadIdx.x == 0) {
+        if (SORTED) {
+            // no global table on this path: nothing to poll
+            if (threadIdx.x == 0) {
+                s_abort = 0;
+                s_live = 0;
+                s_empty = 0;
+                s_bovf = 0;
+            }
+        } else if (threadIdx.x == 0) {
             s_abort = 0;
             if ((blk & 7u) == 0) {
                 unsigned long long f = __hip_atomic_load(
@@ -704,6 +800,7 @@ k_scan_agg_range2(AggParams P, RangeAux R) {
                 __hip_atomic_fetch_add(P.overflow, 1ull, RLX, AGT);
             break;   // host retries with a larger table
         }
+        bool lost = false;   // SORTED: a key of this lane found no LDS slot
         for (uint32_t si = wave; si < R.n_ssts; si += n_waves) {
             const int32_t loff = R.sst_rg_off[si];
             const uint64_t pk0 = R.bound_rows[(size_t)blk * R.n_ssts + si];
@@ -713,7 +810,8 @@ k_scan_agg_range2(AggParams P, RangeAux R) {
             uint32_t row = (uint32_t)pk0;
             const uint32_t epos = (uint32_t)(pk1 >> 32);
             const uint32_t erow = (uint32_t)pk1;
-            while (pos < epos || (pos == epos && row < erow)) {
+            while ((pos < epos || (pos == epos && row < erow)) &&
+                   !(SORTED && __any(lost))) {
                 const RgDesc rg = P.rgs[R.sst_rgs[loff + (int32_t)pos]];
                 const uint64_t* S =
                     (const uint64_t*)hx_ptr(P.blob, P.dec, rg.series_off);
@@ -724,7 +822,8 @@ k_scan_agg_range2(AggParams P, RangeAux R) {
                 const SstDev sst = P.ssts[rg.sst_id];
                 const uint32_t hi = (pos == epos) ? erow : rg.n_rows;
                 const uint32_t nt = rg.n_rows;   // true slice rows
-                for (uint32_t base = row & ~1u; base < hi; base += 128) {
+                for (uint32_t base = row & ~1u;
+                     base < hi && !(SORTED && __any(lost)); base += 128) {
                     const uint32_t r0 = base + 2u * (uint32_t)lane;
                     const uint32_t r1 = r0 + 1u;
                     // load the pair (dwordx4); mask by the ARRAY bound nt —
@@ -816,24 +915,39 @@ k_scan_agg_range2(AggParams P, RangeAux R) {
                     // in-lane pair merge, then direct LDS updates
                     const bool merge = a0 && a1 && (s0 == s1);
                     if (merge) {
-                        lds_update<MM>(P, lkey, lsum, lcnt, lmin, lmax, ne,
-                                       s0, v0 + v1, 2u, fmin(v0, v1),
-                                       fmax(v0, v1), iA, preA);
+                        lost |= !lds_update<MM, SORTED>(
+                            P, lkey, lsum, lcnt, lmin, lmax, ne, s0, v0 + v1,
+                            2u, fmin(v0, v1), fmax(v0, v1), iA, preA);
                     } else {
                         if (a0)
-                            lds_update<MM>(P, lkey, lsum, lcnt, lmin, lmax,
-                                           ne, s0, v0, 1u, v0, v0, iA, preA);
+                            lost |= !lds_update<MM, SORTED>(
+                                P, lkey, lsum, lcnt, lmin, lmax, ne, s0, v0,
+                                1u, v0, v0, iA, preA);
                         if (a1)
-                            lds_update<MM>(P, lkey, lsum, lcnt, lmin, lmax,
-                                           ne, s1, v1, 1u, v1, v1, iB, preB);
+                            lost |= !lds_update<MM, SORTED>(
+                                P, lkey, lsum, lcnt, lmin, lmax, ne, s1, v1,
+                                1u, v1, v1, iB, preB);
                     }
                 }
                 pos++;
                 row = 0;
             }
         }
+        if (SORTED && lost) s_bovf = 1u;
         __syncthreads();
-        {
+        if (SORTED) {
+            if (s_bovf) {
+                // more than ne distinct keys in this block's range: the host
+                // re-partitions with more blocks; emit nothing
+                if (threadIdx.x == 0) {
+                    __hip_atomic_fetch_add(O.block_ovf, 1ull, RLX, AGT);
+                    O.desc[blk] = 0ull;
+                }
+            } else {
+                emit_sorted_run<MM>(O, blk, ne, lkey, lsum, lcnt, lmin, lmax,
+                                    lidx, &s_live, &s_empty, &s_off);
+            }
+        } else {
             unsigned long long live = 0;
             for (uint32_t i = threadIdx.x; i < ne; i += blockDim.x) {
                 if (lkey[i] == KEY_EMPTY) continue;
@@ -855,6 +969,72 @@ k_scan_agg_range2(AggParams P, RangeAux R) {
         my_matched += __shfl_down(my_matched, off, 64);
     if ((threadIdx.x & 63) == 0 && my_matched)
         atomicAdd(P.matched, my_matched);
+}
+
+// ---------------------------------------------------------------------------
+// Placement of the sorted runs. Runs sit in staging in block
+// COMPLETION order; block b's keys all precede block b+1's, so the result
+// is the runs concatenated in blk order. k_place_scan: exclusive prefix of
+// the per-block counts (one workgroup, n_blocks <= 131072); k_place_runs:
+// one wave per run copies every column to its final position and computes
+// avg. Both are no-ops after an overflow (the host retries).
+// ---------------------------------------------------------------------------
+extern "C" __global__ void __launch_bounds__(1024)
+k_place_scan(RangePlace Q) {
+    __shared__ uint32_t part[1024];
+    const uint32_t per = (Q.n_blocks + 1023u) / 1024u;
+    const uint32_t b0 = threadIdx.x * per;
+    const uint32_t b1 = b0 + per < Q.n_blocks ? b0 + per : Q.n_blocks;
+    uint32_t mine = 0;
+    for (uint32_t b = b0; b < b1; b++) mine += (uint32_t)(Q.desc[b] >> 32);
+    part[threadIdx.x] = mine;
+    __syncthreads();
+    for (uint32_t d = 1; d < 1024; d <<= 1) {
+        const uint32_t add = threadIdx.x >= d ? part[threadIdx.x - d] : 0u;
+        __syncthreads();
+        part[threadIdx.x] += add;
+        __syncthreads();
+    }
+    uint32_t run = part[threadIdx.x] - mine;   // exclusive
+    for (uint32_t b = b0; b < b1; b++) {
+        Q.prefix[b] = run;
+        run += (uint32_t)(Q.desc[b] >> 32);
+    }
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+k_place_runs(RangePlace Q) {
+    const unsigned long long total = *Q.cursor;
+    if (*Q.stage_ovf || *Q.block_ovf || total > Q.cap) return;
+    const int lane = threadIdx.x & 63;
+    const uint32_t wave_id = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6;
+    unsigned long long* d_key = Q.dst;
+    double* d_sum = Q.c_sum >= 0 ? (double*)(Q.dst + Q.c_sum * total) : nullptr;
+    unsigned long long* d_cnt = Q.c_cnt >= 0 ? Q.dst + Q.c_cnt * total : nullptr;
+    double* d_min = Q.c_min >= 0 ? (double*)(Q.dst + Q.c_min * total) : nullptr;
+    double* d_max = Q.c_max >= 0 ? (double*)(Q.dst + Q.c_max * total) : nullptr;
+    double* d_avg = Q.c_avg >= 0 ? (double*)(Q.dst + Q.c_avg * total) : nullptr;
+    for (uint32_t b = wave_id; b < Q.n_blocks; b += n_waves) {
+        const uint64_t d = Q.desc[b];
+        const uint32_t cnt = (uint32_t)(d >> 32);
+        if (!cnt) continue;
+        const uint32_t src = (uint32_t)d;
+        const uint32_t dst = Q.prefix[b];
+        // src + cnt <= cap by the reservation; dst + cnt <= total as the
+        // prefix sums the same counts the cursor added up
+        for (uint32_t t = lane; t < cnt; t += 64) {
+            const size_t i = (size_t)src + t, o = (size_t)dst + t;
+            d_key[o] = Q.key[i];
+            const double sm = Q.sum[i];
+            const unsigned long long c = Q.cnt[i];
+            if (d_sum) d_sum[o] = sm;
+            if (d_cnt) d_cnt[o] = c;
+            if (d_min) d_min[o] = Q.vmin[i];
+            if (d_max) d_max[o] = Q.vmax[i];
+            if (d_avg) d_avg[o] = sm / (double)c;
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -2438,24 +2618,43 @@ hipError_t launch_range_bounds(hipStream_t s, const AggParams& p,
     return hipGetLastError();
 }
 
-hipError_t launch_scan_agg_range2(hipStream_t s, const AggParams& p,
-                                  const RangeAux& r, bool minmax) {
-    const size_t lds = (size_t)r.ne * (minmax ? 36 : 20);
-    const void* f = minmax
-                        ? reinterpret_cast<const void*>(&k_scan_agg_range2<true>)
-                        : reinterpret_cast<const void*>(
-                              &k_scan_agg_range2<false>);
+template <bool MM, bool SORTED>
+static hipError_t launch_range2_inst(hipStream_t s, const AggParams& p,
+                                     const RangeAux& r, const RangeOut& o) {
+    // per slot: key 8 + sum 8 + cnt 4 [+ min 8 + max 8] [+ sort index 2]
+    const size_t lds = (size_t)r.ne * ((MM ? 36 : 20) + (SORTED ? 2 : 0));
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(
-            f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            reinterpret_cast<const void*>(&k_scan_agg_range2<MM, SORTED>),
+            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    if (minmax)
-        hipLaunchKernelGGL(k_scan_agg_range2<true>, dim3(r.n_blocks),
-                           dim3(256), lds, s, p, r);
-    else
-        hipLaunchKernelGGL(k_scan_agg_range2<false>, dim3(r.n_blocks),
-                           dim3(256), lds, s, p, r);
+    hipLaunchKernelGGL((k_scan_agg_range2<MM, SORTED>), dim3(r.n_blocks),
+                       dim3(256), lds, s, p, r, o);
+    return hipGetLastError();
+}
+
+hipError_t launch_scan_agg_range2(hipStream_t s, const AggParams& p,
+                                  const RangeAux& r, bool minmax,
+                                  const RangeOut* sorted) {
+    // the sort permutation is u16 and the slot mask needs a power of two
+    if (r.ne == 0 || (r.ne & (r.ne - 1)) || r.ne > 32768u)
+        return hipErrorInvalidValue;
+    if (sorted)
+        return minmax ? launch_range2_inst<true, true>(s, p, r, *sorted)
+                      : launch_range2_inst<false, true>(s, p, r, *sorted);
+    const RangeOut none{};
+    return minmax ? launch_range2_inst<true, false>(s, p, r, none)
+                  : launch_range2_inst<false, false>(s, p, r, none);
+}
+
+hipError_t launch_place_runs(hipStream_t s, const RangePlace& q) {
+    if (q.n_blocks == 0 || q.n_blocks > 131072u) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_place_scan, dim3(1), dim3(1024), 0, s, q);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_place_runs, dim3(grid_for(q.n_blocks, 4)), dim3(256),
+                       0, s, q);
     return hipGetLastError();
 }
 
