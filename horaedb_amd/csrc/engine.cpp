@@ -385,7 +385,12 @@ struct DevPlan {
     uint32_t slab_stride = 0;
     uint8_t* t_bstore = nullptr;    // direct-indexed bucket accumulators
     uint64_t bstore_cap = 0;
-    unsigned long long* d_counters = nullptr;  // fill, overflow, matched, n_out
+    // six words, zeroed per attempt. Table route: 0 fill, 1 overflow,
+    // 2 matched. Sorted-run route: 0 cursor (= group count), 1 staging
+    // overflow, 2 matched, 4 block overflow. Decode: 1 error flag. Word 3 is
+    // free (it counted the range kernel's LDS misses until the table flush
+    // was removed); 5 is unused.
+    unsigned long long* d_counters = nullptr;
     uint64_t* d_sset = nullptr;
     size_t sset_cap = 0;
     uint64_t sset_empty = ~0ull;
@@ -1510,19 +1515,23 @@ static hx_status ensure_range(DevPlan& plan, const hx::AggParams& base,
     const double x_est = 0.5 * (x_lo + x_hi);
     plan.range_xest = x_est;
     double target = 650.0;   // series per block: ne=1024 at load ~0.3.
-                             // Load 0.6 put ~0.3% of heads through the
-                             // global fallback whose per-claim fill adds
-                             // re-serialize at the coherence point —
-                             // 13.5 ms vs 7.5 ms at the 1B shape.
+                             // History: measured when an LDS miss went to
+                             // the global table — load 0.6 sent ~0.3% of
+                             // heads there, 13.5 ms vs 7.5 ms at the 1B
+                             // shape. Today a block that overflows ne costs
+                             // a full rerun of the kernel with twice the
+                             // blocks, so the margin still pays.
     if (const char* e = getenv("HX_RANGE_TARGET")) target = atof(e);
     uint32_t nb = 512;
     while (nb < (uint32_t)std::min(1e9, x_est * 1.3 / target) &&
            nb < (1u << 17))
         nb <<= 1;
     // safety floor against a residual under-estimate: cap rows per block
-    // at 16384 (64-SST shapes: ~256 rows/sst/block). Empty or tiny blocks
-    // are cheap; an LDS-table overflow (the fallback path) is a global-RMW
-    // storm (r01: 286M of 320M updates went global at the 1B shape).
+    // at 32768 (64-SST shapes: ~512 rows/sst/block). Empty or tiny blocks
+    // are cheap; a block that overflows its LDS table reruns the whole
+    // kernel with twice the blocks. History: the floor dates from r01, when
+    // an overflow spilled to the global table instead (286M of 320M updates
+    // went global at the 1B shape).
     if (!getenv("HX_RANGE_TARGET"))   // explicit target: trust the caller
         while ((double)nb * 32768.0 < staged && nb < (1u << 17)) nb <<= 1;
     while (nb < min_nb && nb < (1u << 17)) nb <<= 1;
@@ -1672,7 +1681,7 @@ static hx_status exec_range_sorted(hx_prepared* P, DevPlan& plan,
         if (est != HX_OK) return est;
         hipEvent_t e0 = plan.ev[0], e1 = plan.ev[1];
         HIP_TRY(hipEventRecord(e0, s));
-        hipError_t ke = hx::launch_scan_agg_range2(s, A, R, mm, &O);
+        hipError_t ke = hx::launch_scan_agg_range2(s, A, R, mm, O);
         if (ke != hipSuccess)
             return fail(HX_ERR_HIP,
                         std::string("range kernel launch failed: ") +
@@ -1741,102 +1750,64 @@ static hx_status exec_range_sorted(hx_prepared* P, DevPlan& plan,
     return HX_OK;
 }
 
-hx_status exec_plan(hx_prepared* P, DevPlan& plan, const hx_agg_spec* agg,
-                    HostTable& out, double* agg_kernel_ms,
-                    unsigned long long* matched_out) {
-    if (P->h->bytes_value)
-        return fail(HX_ERR_UNSUPPORTED,
-                    "aggregates over Binary value columns are undefined "
-                    "(scan the rows with hx_scan instead)");
-    HIP_TRY(hipSetDevice(plan.device));
-    hipStream_t s = plan.stream;
-    const uint32_t ops = kernel_ops(agg->ops);
-    const bool bucket = agg->bucket_ms > 0;
-
-    hx_status sst_ = ensure_sset(P, plan);
-    if (sst_ != HX_OK) return sst_;
-
-    // decode results persist across exec calls on one prepared scan; for
-    // benchmarking encoded/compressed workloads HX_REDECODE=1 forces every
-    // step to repeat the decompress/decode stage (no cached decode output
-    // inside the timed region).
-    if (getenv("HX_REDECODE")) plan.decoded = false;
-    hx_status dst_ = ensure_decoded(plan, s);
-    if (dst_ != HX_OK) return dst_;
-
-    // one-CAS key claim: series-only grouping with a stats-proven sentinel
-    // (HX_FORCE_STATE=1 forces the generic state-word path for A/B runs).
-    // Bucket queries take the DIRECT-INDEXED path when the bucket range
-    // (known exactly from the scan range clamped to the catalog) fits a
-    // dense per-slot accumulator row: table keyed by series only, bucket
-    // becomes an array index — no (series,bucket) hashing at all.
+// Direct-indexed bucket decision (bucket queries, key-claim safe): when the
+// bucket range — known exactly from the scan range clamped to the catalog —
+// fits a dense per-slot accumulator row, the table is keyed by series only
+// and the bucket becomes an array index: no (series,bucket) hashing at all.
+// n_buckets == 0 means "take the generic state-word path".
+struct BucketPlan {
     int64_t lo_bucket = 0;
     uint32_t n_buckets = 0;
-    uint32_t bstride = 0;
-    if (bucket && P->key_claim_safe && !getenv("HX_FORCE_STATE")) {
-        int64_t lo_ts = P->spec.range.start, hi_ts = P->spec.range.end;
-        int64_t cat_lo = INT64_MAX, cat_hi = INT64_MIN;
-        for (const auto& c : P->h->ssts) {
-            cat_lo = std::min(cat_lo, c.ts_min);
-            cat_hi = std::max(cat_hi, c.ts_max);
-        }
-        if (cat_lo <= cat_hi) {
-            lo_ts = std::max(lo_ts, cat_lo);
-            hi_ts = std::min(hi_ts, cat_hi + 1);
-        }
-        if (lo_ts < hi_ts) {
-            auto fdiv = [&](int64_t t) {
-                int64_t q = t / agg->bucket_ms;
-                if ((t % agg->bucket_ms) != 0 && t < 0) q--;
-                return q;
-            };
-            lo_bucket = fdiv(lo_ts);
-            int64_t nb = fdiv(hi_ts - 1) - lo_bucket + 1;
-            bstride = (agg->ops & (HX_AGG_MIN | HX_AGG_MAX)) ? 32u : 16u;
-            // memory cap: fall back to the generic path beyond ~24 GB
-            uint64_t est_slots = std::max<uint64_t>(
-                1 << 16, next_pow2_u32((uint64_t)plan.rows_scanned / 32));
-            if (nb > 0 &&
-                (uint64_t)nb * est_slots * bstride <= (24ull << 30)) {
-                n_buckets = (uint32_t)nb;
-            } else {
-                bstride = 0;
-            }
-        }
-    }
-    int32_t key_claim =
-        ((!bucket || n_buckets) && P->key_claim_safe &&
-         !getenv("HX_FORCE_STATE")) ? 1 : 0;
+    uint32_t bstride = 0;   // 16 {sum,cnt} or 32 {+min,max}
+};
 
-    // series-range partition: built once per prepared, before
-    // table sizing so its distinct-series estimate can size the table
-    // (prevents a saturated first pass + retry)
-    bool use_range = !bucket && key_claim && !n_buckets;
-    if (const char* renv = getenv("HX_RANGE"))
-        use_range = use_range && atoi(renv) != 0;
-    if (use_range && !plan.range_ready) {
-        hx::AggParams base{};
-        base.rgs = plan.d_rgs;
-        base.blob = plan.d_blob;
-        base.dec = plan.d_dec;
-        hx_status rs = ensure_range(plan, base);
-        if (rs != HX_OK) return rs;
+static BucketPlan direct_buckets(hx_prepared* P, const DevPlan& plan,
+                                 const hx_agg_spec* agg) {
+    BucketPlan bp;
+    if (agg->bucket_ms <= 0 || !P->key_claim_safe || getenv("HX_FORCE_STATE"))
+        return bp;
+    int64_t lo_ts = P->spec.range.start, hi_ts = P->spec.range.end;
+    int64_t cat_lo = INT64_MAX, cat_hi = INT64_MIN;
+    for (const auto& c : P->h->ssts) {
+        cat_lo = std::min(cat_lo, c.ts_min);
+        cat_hi = std::max(cat_hi, c.ts_max);
     }
-    if (use_range && !plan.range_ready) use_range = false;
+    if (cat_lo <= cat_hi) {
+        lo_ts = std::max(lo_ts, cat_lo);
+        hi_ts = std::min(hi_ts, cat_hi + 1);
+    }
+    if (lo_ts >= hi_ts) return bp;
+    auto fdiv = [&](int64_t t) {
+        int64_t q = t / agg->bucket_ms;
+        if ((t % agg->bucket_ms) != 0 && t < 0) q--;
+        return q;
+    };
+    bp.lo_bucket = fdiv(lo_ts);
+    const int64_t nb = fdiv(hi_ts - 1) - bp.lo_bucket + 1;
+    const uint32_t bstride =
+        (agg->ops & (HX_AGG_MIN | HX_AGG_MAX)) ? 32u : 16u;
+    // memory cap: take the generic path beyond ~24 GB
+    const uint64_t est_slots = std::max<uint64_t>(
+        1 << 16, next_pow2_u32((uint64_t)plan.rows_scanned / 32));
+    if (nb > 0 && (uint64_t)nb * est_slots * bstride <= (24ull << 30)) {
+        bp.n_buckets = (uint32_t)nb;
+        bp.bstride = bstride;
+    }
+    return bp;
+}
 
-    // sorted-run result path. HX_RANGE_SORTED=0 keeps the range
-    // kernel's flush into the global table for A/B runs.
-    bool sorted = use_range && !plan.sorted_gave_up;
-    if (const char* senv = getenv("HX_RANGE_SORTED"))
-        sorted = sorted && atoi(senv) != 0;
-    if (sorted) {
-        bool done = false;
-        hx_status rs = exec_range_sorted(P, plan, agg, ops, out,
-                                         agg_kernel_ms, matched_out, &done);
-        if (rs != HX_OK || done) return rs;
-    }
-    // a block range that will not fit LDS: the wave kernel has no such limit
-    if (plan.sorted_gave_up) use_range = false;
+// The global-table route: every grouping the range path does not take
+// (buckets, the state-word path, HX_RANGE=0, a range plan that gave up).
+// The wave kernel (k_scan_agg) aggregates into the hash table, retried with
+// a larger table on overflow; then compaction, sort, gather and one D2H.
+static hx_status exec_table(hx_prepared* P, DevPlan& plan,
+                            const hx_agg_spec* agg, uint32_t ops,
+                            BucketPlan bp, int32_t key_claim, HostTable& out,
+                            double* agg_kernel_ms,
+                            unsigned long long* matched_out) {
+    hipStream_t s = plan.stream;
+    const bool bucket = agg->bucket_ms > 0;
+    const bool mm = (ops & (HX_AGG_MIN | HX_AGG_MAX)) != 0;
 
     // table size heuristic; grows on overflow
     uint32_t slots = plan.slots;
@@ -1848,7 +1819,8 @@ hx_status exec_plan(hx_prepared* P, DevPlan& plan, const hx_agg_spec* agg,
                  // generic (series,bucket) hashing needs generous sizing;
                  // the direct-indexed path is keyed by series only
                  (uint64_t)plan.rows_scanned /
-                     ((bucket && !n_buckets) ? 2 : 32)));
+                     ((bucket && !bp.n_buckets) ? 2 : 32)));
+        // the range partition's distinct-series estimate, when one was built
         if (plan.range_xest > 0 && key_claim && !bucket) {
             uint32_t rs = next_pow2_u32((uint64_t)(plan.range_xest * 1.4));
             if (rs > slots) slots = rs;
@@ -1860,8 +1832,8 @@ hx_status exec_plan(hx_prepared* P, DevPlan& plan, const hx_agg_spec* agg,
     for (int attempt = 0; attempt < 4; attempt++) {
         hx_status st = alloc_table(plan, slots, ops, key_claim);
         if (st != HX_OK) return st;
-        if (n_buckets) {
-            uint64_t need_b = (uint64_t)slots * n_buckets * bstride;
+        if (bp.n_buckets) {
+            uint64_t need_b = (uint64_t)slots * bp.n_buckets * bp.bstride;
             if (need_b > plan.bstore_cap) {
                 if (plan.t_bstore) hipFree(plan.t_bstore);
                 plan.t_bstore = nullptr;
@@ -1874,66 +1846,35 @@ hx_status exec_plan(hx_prepared* P, DevPlan& plan, const hx_agg_spec* agg,
         if (key_claim) {
             HIP_TRY(hx::launch_init_slab(s, plan.t_slab, slots,
                                          plan.slab_stride));
-            if (n_buckets)
+            if (bp.n_buckets)
                 HIP_TRY(hx::launch_init_accum_rows(
-                    s, plan.t_bstore, (size_t)slots * n_buckets, bstride,
-                    (ops & (HX_AGG_MIN | HX_AGG_MAX)) != 0));
+                    s, plan.t_bstore, (size_t)slots * bp.n_buckets,
+                    bp.bstride, mm));
         } else {
-            HIP_TRY(hx::launch_init_state_slab(
-                s, plan.t_slab, slots, plan.slab_stride,
-                (ops & (HX_AGG_MIN | HX_AGG_MAX)) != 0));
+            HIP_TRY(hx::launch_init_state_slab(s, plan.t_slab, slots,
+                                               plan.slab_stride, mm));
         }
         HIP_TRY(hipMemsetAsync(plan.d_counters, 0, 48, s));
 
-        hx::AggParams A{};
-        A.rgs = plan.d_rgs;
-        A.n_rgs = (uint32_t)plan.rgs.size();
-        A.ssts = plan.d_ssts;
-        A.clusters = plan.d_clusters;
-        A.cluster_members = plan.d_members;
-        A.blob = plan.d_blob;
-        A.dec = plan.d_dec;
-        A.ts_lo = P->spec.range.start;
-        A.ts_hi = P->spec.range.end;
-        A.sset = plan.d_sset;
-        A.sset_mask = plan.sset_mask;
-        A.sset_empty = plan.sset_empty;
-        A.use_sset = plan.d_sset ? 1 : 0;
+        hx::AggParams A = base_params(P, plan);
         A.bucket_ms = bucket ? agg->bucket_ms : 0;
-        A.ops = n_buckets ? (ops | HX_AGG_COUNT) : ops;  // cnt = liveness
+        A.ops = bp.n_buckets ? (ops | HX_AGG_COUNT) : ops;  // cnt = liveness
         A.key_claim = key_claim;
-        A.lo_bucket = lo_bucket;
-        A.n_buckets = n_buckets;
-        A.bstride = bstride;
+        A.lo_bucket = bp.lo_bucket;
+        A.n_buckets = bp.n_buckets;
+        A.bstride = bp.bstride;
         A.bstore = plan.t_bstore;
         A.table = agg_table(plan);
         A.fill_limit = (unsigned long long)(double(slots) * 0.85);
         A.fill = plan.d_counters + 0;
         A.overflow = plan.d_counters + 1;
         A.matched = plan.d_counters + 2;
-        A.fallback = plan.d_counters + 3;
 
         hx_status est = ensure_events(plan);
         if (est != HX_OK) return est;
         hipEvent_t e0 = plan.ev[0], e1 = plan.ev[1];
         HIP_TRY(hipEventRecord(e0, s));
-        if (use_range) {
-            uint32_t ne = 1024;
-            if (const char* e = getenv("HX_RANGE_NE"))
-                ne = (uint32_t)strtoul(e, nullptr, 10);
-            hx::RangeAux R{plan.d_range_bounds, plan.d_bound_rows,
-                           plan.d_sst_rgs,     plan.d_sst_rg_off,
-                           plan.d_sst_rg_cnt,  (uint32_t)plan.ssts.size(),
-                           plan.range_nblocks, ne};
-            hipError_t re2 = hx::launch_scan_agg_range2(
-                s, A, R, (ops & (HX_AGG_MIN | HX_AGG_MAX)) != 0, nullptr);
-            if (re2 != hipSuccess)
-                return fail(HX_ERR_HIP,
-                            std::string("range kernel launch failed: ") +
-                                hipGetErrorString(re2));
-        }
-        if (!use_range)
-            HIP_TRY(hx::launch_scan_agg(s, A, 0));
+        HIP_TRY(hx::launch_scan_agg(s, A, 0));
         HIP_TRY(hipEventRecord(e1, s));
         HIP_TRY(hipStreamSynchronize(s));
         float ms = 0;
@@ -1941,24 +1882,21 @@ hx_status exec_plan(hx_prepared* P, DevPlan& plan, const hx_agg_spec* agg,
         HIP_TRY(hipMemcpy(counters, plan.d_counters, 48, hipMemcpyDeviceToHost));
         if (getenv("HX_DEBUG"))
             fprintf(stderr,
-                    "[hx] exec attempt=%d kernel=%s slots=%u nb=%u ne_env=%s "
-                    "xest=%.0f kernel_ms=%.2f fill=%llu overflow=%llu "
-                    "matched=%llu lds_fallback=%llu\n",
-                    attempt, use_range ? "range" : "wave", slots,
-                    plan.range_nblocks, getenv("HX_RANGE_NE") ?: "-",
-                    plan.range_xest, ms, counters[0], counters[1],
-                    counters[2], counters[3]);
+                    "[hx] exec attempt=%d kernel=wave slots=%u xest=%.0f "
+                    "kernel_ms=%.2f fill=%llu overflow=%llu matched=%llu\n",
+                    attempt, slots, plan.range_xest, ms, counters[0],
+                    counters[1], counters[2]);
         if (counters[1] == 0) {  // no overflow
             *agg_kernel_ms = ms;
             break;
         }
         if (attempt == 3)
             return fail(HX_ERR_HIP, "aggregate table overflow persisted");
-        if (n_buckets) {
+        if (bp.n_buckets) {
             // direct-indexed bucket overflow (e.g. footer ts stats under-
             // reported the range): fall back to the generic hashed path
-            n_buckets = 0;
-            bstride = 0;
+            bp.n_buckets = 0;
+            bp.bstride = 0;
             key_claim = 0;
         } else {
             slots = slots >= (1u << 28) ? slots : slots * 4;
@@ -1976,8 +1914,8 @@ hx_status exec_plan(hx_prepared* P, DevPlan& plan, const hx_agg_spec* agg,
     // direct-indexed buckets => up to fill x n_buckets groups, but never
     // more than the surviving-row count
     uint64_t cap64 = fill;
-    if (n_buckets)
-        cap64 = std::min<uint64_t>(fill * (uint64_t)n_buckets, counters[2]);
+    if (bp.n_buckets)
+        cap64 = std::min<uint64_t>(fill * (uint64_t)bp.n_buckets, counters[2]);
     if (cap64 > 0xFFFFFFFFull)
         return fail(HX_ERR_UNSUPPORTED, "result exceeds 2^32 groups");
     const uint32_t n = (uint32_t)cap64;
@@ -2019,8 +1957,8 @@ hx_status exec_plan(hx_prepared* P, DevPlan& plan, const hx_agg_spec* agg,
     HIP_TRY(hipMemsetAsync(d_nout, 0, 8, s));
     hx::CompactOut co{c_series, c_bucket, c_sum, c_cnt, c_min, c_max, d_nout};
     HIP_TRY(hx::launch_compact(s, agg_table(plan), plan.slots, key_claim,
-                               bucket ? agg->bucket_ms : 0, lo_bucket,
-                               n_buckets, bstride, plan.t_bstore, co,
+                               bucket ? agg->bucket_ms : 0, bp.lo_bucket,
+                               bp.n_buckets, bp.bstride, plan.t_bstore, co,
                                compact_scratch));
     unsigned long long n_groups64 = 0;
     HIP_TRY(hipStreamSynchronize(s));
@@ -2085,6 +2023,66 @@ hx_status exec_plan(hx_prepared* P, DevPlan& plan, const hx_agg_spec* agg,
     out.vmax = has_max ? (double*)(hb + off_max * ng) : nullptr;
     out.avg = has_avg ? (double*)(hb + size_t(n_core) * ng) : nullptr;
     return HX_OK;
+}
+
+// Aggregate one device's plan into `out` (sorted by series[, bucket]). Two
+// routes: series-only grouping with a key-claim-safe sentinel takes the range
+// path (exec_range_sorted); everything else, and a range plan that gave up,
+// takes the global table (exec_table).
+hx_status exec_plan(hx_prepared* P, DevPlan& plan, const hx_agg_spec* agg,
+                    HostTable& out, double* agg_kernel_ms,
+                    unsigned long long* matched_out) {
+    if (P->h->bytes_value)
+        return fail(HX_ERR_UNSUPPORTED,
+                    "aggregates over Binary value columns are undefined "
+                    "(scan the rows with hx_scan instead)");
+    HIP_TRY(hipSetDevice(plan.device));
+    const uint32_t ops = kernel_ops(agg->ops);
+    const bool bucket = agg->bucket_ms > 0;
+
+    hx_status sst_ = ensure_sset(P, plan);
+    if (sst_ != HX_OK) return sst_;
+
+    // decode results persist across exec calls on one prepared scan; for
+    // benchmarking encoded/compressed workloads HX_REDECODE=1 forces every
+    // step to repeat the decompress/decode stage (no cached decode output
+    // inside the timed region).
+    if (getenv("HX_REDECODE")) plan.decoded = false;
+    hx_status dst_ = ensure_decoded(plan, plan.stream);
+    if (dst_ != HX_OK) return dst_;
+
+    // one-CAS key claim: series-only grouping, or direct-indexed buckets,
+    // with a stats-proven sentinel (HX_FORCE_STATE=1 forces the generic
+    // state-word path for A/B runs)
+    const BucketPlan bp = direct_buckets(P, plan, agg);
+    const int32_t key_claim =
+        ((!bucket || bp.n_buckets) && P->key_claim_safe &&
+         !getenv("HX_FORCE_STATE")) ? 1 : 0;
+
+    // series-range partition: built once per prepared. A plan
+    // whose sorted path gave up (a block range that will not fit LDS; the
+    // wave kernel has no such limit) stays on the table route and does not
+    // rebuild the partition.
+    bool use_range =
+        !bucket && key_claim && !bp.n_buckets && !plan.sorted_gave_up;
+    if (const char* renv = getenv("HX_RANGE"))
+        use_range = use_range && atoi(renv) != 0;
+    if (use_range && !plan.range_ready) {
+        hx::AggParams base{};
+        base.rgs = plan.d_rgs;
+        base.blob = plan.d_blob;
+        base.dec = plan.d_dec;
+        hx_status rs = ensure_range(plan, base);
+        if (rs != HX_OK) return rs;
+    }
+    if (use_range && plan.range_ready) {
+        bool done = false;
+        hx_status rs = exec_range_sorted(P, plan, agg, ops, out,
+                                         agg_kernel_ms, matched_out, &done);
+        if (rs != HX_OK || done) return rs;
+    }
+    return exec_table(P, plan, agg, ops, bp, key_claim, out, agg_kernel_ms,
+                      matched_out);
 }
 
 }  // namespace

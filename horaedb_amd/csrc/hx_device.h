@@ -92,19 +92,20 @@ struct AggParams {
     uint32_t n_buckets;            // 0 => generic state-word path
     uint32_t bstride;              // 16 {sum,cnt} or 32 {+min,max}
     uint8_t* bstore;
+    // global-table bookkeeping: used by k_scan_agg only (the range kernel
+    // never touches the table)
     unsigned long long fill_limit; // early-abort when fill exceeds this
     unsigned long long* fill;      // claimed slots
     unsigned long long* overflow;  // !=0 => rerun with a larger table
     unsigned long long* matched;   // rows surviving filter+dedup
-    unsigned long long* fallback;  // LDS-table misses routed to global RMWs
 };
 
 // Series-range partitioned aggregation (k_scan_agg_range2): the
 // series space is split at equal-sample quantile boundaries; block b owns
 // series in [bounds[b], bounds[b+1]) across ALL SSTs, accumulating into an
-// LDS table flushed once — global-table RMWs drop from one per 64-row-
-// window run to one per (block, series). Row bounds per (block, sst) are
-// precomputed by k_range_bounds (64-ary parallel lower_bound) and cached.
+// LDS table that leaves the block once, as a sorted run (RangeOut) — no
+// global-table RMWs at all. Row bounds per (block, sst) are precomputed by
+// k_range_bounds (64-ary parallel lower_bound) and cached.
 struct RangeAux {
     const uint64_t* bounds;      // n_blocks+1 ascending series boundaries
     const uint64_t* bound_rows;  // (n_blocks+1) x n_ssts packed (pos<<32|row)

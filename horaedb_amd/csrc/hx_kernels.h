@@ -36,12 +36,11 @@ hipError_t launch_sample_series(hipStream_t s, const RgDesc* rgs,
                                 const uint8_t* dec, uint64_t* out);
 hipError_t launch_range_bounds(hipStream_t s, const AggParams& p,
                                const RangeAux& r, uint64_t* out);
-// sorted != nullptr: each block emits its groups as one key-ordered run into
-// *sorted (no global table); launch_place_runs then assembles the result.
-// sorted == nullptr: the blocks flush into p.table (HX_RANGE_SORTED=0).
+// Each block emits its groups as one key-ordered run into `out` (p.table is
+// not used); launch_place_runs then assembles the result.
 hipError_t launch_scan_agg_range2(hipStream_t s, const AggParams& p,
                                   const RangeAux& r, bool minmax,
-                                  const RangeOut* sorted);
+                                  const RangeOut& out);
 // Exclusive scan of the run counts in blk order, then one copy of every run
 // to its final position in the contiguous SoA result (avg computed here).
 hipError_t launch_place_runs(hipStream_t s, const RangePlace& q);

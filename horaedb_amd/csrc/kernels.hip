@@ -144,8 +144,7 @@ __device__ __forceinline__ void agg_update_keycas(const AggParams& P, uint64_t s
                                                   unsigned long long cnt,
                                                   double mn, double mx,
                                                   uint32_t hint_i = 0xFFFFFFFFu,
-                                                  uint64_t hint_k = 0,
-                                                  bool count_fill = true) {
+                                                  uint64_t hint_k = 0) {
     const uint32_t stride = P.table.stride;
     uint32_t i = (uint32_t)mix64(s) & P.table.mask;
     if (hint_i == i && hint_k == s) {  // prefetched probe already matched
@@ -162,11 +161,10 @@ __device__ __forceinline__ void agg_update_keycas(const AggParams& P, uint64_t s
                     &expected, s, RLX, RLX, AGT)) {
                 // P.fill is ONE word: per-claim increments serialize at the
                 // coherence point and backpressure the whole vmcnt pipeline
-                // (measured ~17 ms of the 24 ms launch). Callers that count
-                // claims in bulk (the range kernel's flush) pass
-                // count_fill = false and add per-block totals instead.
-                if (count_fill)
-                    __hip_atomic_fetch_add(P.fill, 1ull, RLX, AGT);
+                // (measured ~17 ms of a 24 ms launch). The wave kernel still
+                // pays this; the one caller that counted claims in bulk (the
+                // range kernel's table flush) is gone.
+                __hip_atomic_fetch_add(P.fill, 1ull, RLX, AGT);
                 k = s;
             } else {
                 k = expected;
@@ -238,11 +236,9 @@ __device__ __forceinline__ void agg_update(const AggParams& P, uint64_t s,
                                            unsigned long long cnt,
                                            double mn, double mx,
                                            uint32_t hint_i = 0xFFFFFFFFu,
-                                           uint64_t hint_k = 0,
-                                           bool count_fill = true) {
+                                           uint64_t hint_k = 0) {
     if (P.key_claim) {
-        agg_update_keycas(P, s, b, vsum, cnt, mn, mx, hint_i, hint_k,
-                          count_fill);
+        agg_update_keycas(P, s, b, vsum, cnt, mn, mx, hint_i, hint_k);
         return;
     }
     // AoS slot: {state u32, pad u32, series u64, bucket i64, sum, cnt
@@ -505,8 +501,8 @@ k_scan_agg(AggParams P) {
 // gangs lose to series-position jitter (sqrt-scale fluctuations between
 // SSTs dwarf a window), so the partition here is by series VALUE: block b
 // owns [bounds[b], bounds[b+1]) across every SST; its series fit an LDS
-// table by construction, flushed once — global RMWs drop from one per
-// window-run (~rows/1.6) to one per (block, series).
+// table by construction and leave it once, as one key-ordered run — no
+// global RMW per row or per window-run at all.
 // ---------------------------------------------------------------------------
 
 // Stride-512 series samples per rg slice (16 fixed slots, ~0 padding): the
@@ -607,9 +603,9 @@ k_range_bounds(AggParams P, RangeAux R, uint64_t* __restrict__ out) {
 //     own pair in registers (36% of adjacent rows share a series at the
 //     headline shape) and issues its 1-2 LDS updates directly.
 // Per block: reset the LDS table, scan the block's series range in every
-// SST, then either emit the live slots as one key-ordered run (SORTED, the
-// default: DESIGN §4) or flush each to the global table once (!SORTED, the
-// HX_RANGE_SORTED=0 A/B route).
+// SST, then emit the live slots as one key-ordered run. The
+// kernel never touches the global hash table: it has no saturation poll,
+// and its only overflow policy is "report the block, emit nothing".
 // ---------------------------------------------------------------------------
 
 // Add one (key, partial aggregate) to the block's LDS table, first probe at
@@ -618,22 +614,19 @@ k_range_bounds(AggParams P, RangeAux R, uint64_t* __restrict__ out) {
 // critical path. A stale EMPTY only re-routes through the CAS (keys
 // transition EMPTY->key exactly once), never corrupts.
 //
-// SORTED (the sorted-run epilogue): the probe walks the WHOLE table, so a
-// key that finds no slot proves the block holds more than ne distinct keys;
-// that returns false (block overflow, the host re-partitions) and nothing
-// goes to global memory. !SORTED keeps the 16-probe limit and routes a miss
-// to the global table.
-template <bool MM, bool SORTED>
-__device__ __forceinline__ bool lds_update(const AggParams& P, uint64_t* lkey,
-                                           double* lsum, unsigned int* lcnt,
+// The probe walks the WHOLE table, so a key that finds no slot proves the
+// block holds more than ne distinct keys; that returns false (block
+// overflow, the host re-partitions). Nothing here goes to global memory.
+template <bool MM>
+__device__ __forceinline__ bool lds_update(uint64_t* lkey, double* lsum,
+                                           unsigned int* lcnt,
                                            unsigned long long* lmin,
                                            unsigned long long* lmax,
                                            uint32_t ne, uint64_t sv, double v,
                                            uint32_t cnt, double mn, double mx,
                                            uint32_t i, uint64_t pre) {
-    const uint32_t limit = SORTED ? ne : 16u;
 #pragma unroll 1
-    for (uint32_t probes = 0; probes < limit; probes++) {
+    for (uint32_t probes = 0; probes < ne; probes++) {
         uint64_t kk = (probes == 0) ? pre : lkey[i];
         if (kk == KEY_EMPTY) {
             uint64_t old = atomicCAS(&lkey[i], KEY_EMPTY, sv);
@@ -650,22 +643,10 @@ __device__ __forceinline__ bool lds_update(const AggParams& P, uint64_t* lkey,
         }
         i = (i + 1) & (ne - 1);
     }
-    if (SORTED) return false;
-    // LDS table full: direct global update (count it — a non-trivial rate
-    // here turns the kernel into a global-RMW storm; wave-aggregated so the
-    // counter itself cannot serialize)
-    if (P.fallback) {
-        const unsigned long long mk = __ballot(1);
-        const int lane = (int)(threadIdx.x & 63);
-        if ((__ffsll(mk) - 1) == lane)
-            __hip_atomic_fetch_add(P.fallback,
-                                   (unsigned long long)__popcll(mk), RLX, AGT);
-    }
-    agg_update(P, sv, 0, v, cnt, mn, mx);
-    return true;
+    return false;
 }
 
-// Sorted-run epilogue of one block (SORTED instances): order the live LDS
+// Sorted-run epilogue of one block: order the live LDS
 // entries by ascending unsigned key and write them as one contiguous run.
 // The slot function is order-preserving but linear probing displaces keys
 // (and wraps), so the order is established exactly: live slot indices are
@@ -738,11 +719,10 @@ __device__ __forceinline__ void emit_sorted_run(
     }
 }
 
-template <bool MM, bool SORTED>
+template <bool MM>
 __global__ void __launch_bounds__(256)
 k_scan_agg_range2(AggParams P, RangeAux R, RangeOut O) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    __shared__ int s_abort;
     __shared__ uint32_t s_live, s_empty, s_bovf;
     __shared__ unsigned long long s_off;
     const uint32_t ne = R.ne;
@@ -751,34 +731,17 @@ k_scan_agg_range2(AggParams P, RangeAux R, RangeOut O) {
     unsigned long long* lmin = (unsigned long long*)(smem + (size_t)ne * 16);
     unsigned long long* lmax = (unsigned long long*)(smem + (size_t)ne * 24);
     unsigned int* lcnt = (unsigned int*)(smem + (size_t)ne * (MM ? 32 : 16));
-    unsigned short* lidx =   // SORTED only: sort permutation, 2 B per slot
+    unsigned short* lidx =   // sort permutation, 2 B per slot
         (unsigned short*)(smem + (size_t)ne * (MM ? 36 : 20));
     const int lane = threadIdx.x & 63;
     const uint32_t wave = threadIdx.x >> 6;
     const uint32_t n_waves = blockDim.x >> 6;
     unsigned long long my_matched = 0;
     for (uint32_t blk = blockIdx.x; blk < R.n_blocks; blk += gridDim.x) {
-        // saturation early-abort, polled by ONE thread per block on every
-        // 8th block: P.fill's line is evicted chip-wide by every agent-scope
-        // claim, so ANY load of it is served at the coherence point (~88/us
-        // single-word) — polling per (wave, sst) serialized the whole kernel
-        // (+23 ms at the 1B shape). A stale read only delays the abort; the
-        // probe cap still bounds a doomed pass.
-        if (SORTED) {
-            // no global table on this path: nothing to poll
-            if (threadIdx.x == 0) {
-                s_abort = 0;
-                s_live = 0;
-                s_empty = 0;
-                s_bovf = 0;
-            }
-        } else if (threadIdx.x == 0) {
-            s_abort = 0;
-            if ((blk & 7u) == 0) {
-                unsigned long long f = __hip_atomic_load(
-                    P.fill, RLX, __HIP_MEMORY_SCOPE_WORKGROUP);
-                if (f > P.fill_limit) s_abort = 1;
-            }
+        if (threadIdx.x == 0) {
+            s_live = 0;
+            s_empty = 0;
+            s_bovf = 0;
         }
         for (uint32_t i = threadIdx.x; i < ne; i += blockDim.x) {
             lkey[i] = KEY_EMPTY;
@@ -795,12 +758,7 @@ k_scan_agg_range2(AggParams P, RangeAux R, RangeOut O) {
         const uint64_t ihi = R.bounds[blk + 1];
         const double islope = (double)ne / ((double)(ihi - ilo) + 1.0);
         __syncthreads();
-        if (s_abort) {
-            if (threadIdx.x == 0)
-                __hip_atomic_fetch_add(P.overflow, 1ull, RLX, AGT);
-            break;   // host retries with a larger table
-        }
-        bool lost = false;   // SORTED: a key of this lane found no LDS slot
+        bool lost = false;   // a key of this lane found no LDS slot
         for (uint32_t si = wave; si < R.n_ssts; si += n_waves) {
             const int32_t loff = R.sst_rg_off[si];
             const uint64_t pk0 = R.bound_rows[(size_t)blk * R.n_ssts + si];
@@ -811,7 +769,7 @@ k_scan_agg_range2(AggParams P, RangeAux R, RangeOut O) {
             const uint32_t epos = (uint32_t)(pk1 >> 32);
             const uint32_t erow = (uint32_t)pk1;
             while ((pos < epos || (pos == epos && row < erow)) &&
-                   !(SORTED && __any(lost))) {
+                   !__any(lost)) {
                 const RgDesc rg = P.rgs[R.sst_rgs[loff + (int32_t)pos]];
                 const uint64_t* S =
                     (const uint64_t*)hx_ptr(P.blob, P.dec, rg.series_off);
@@ -823,7 +781,7 @@ k_scan_agg_range2(AggParams P, RangeAux R, RangeOut O) {
                 const uint32_t hi = (pos == epos) ? erow : rg.n_rows;
                 const uint32_t nt = rg.n_rows;   // true slice rows
                 for (uint32_t base = row & ~1u;
-                     base < hi && !(SORTED && __any(lost)); base += 128) {
+                     base < hi && !__any(lost); base += 128) {
                     const uint32_t r0 = base + 2u * (uint32_t)lane;
                     const uint32_t r1 = r0 + 1u;
                     // load the pair (dwordx4); mask by the ARRAY bound nt —
@@ -915,17 +873,17 @@ k_scan_agg_range2(AggParams P, RangeAux R, RangeOut O) {
                     // in-lane pair merge, then direct LDS updates
                     const bool merge = a0 && a1 && (s0 == s1);
                     if (merge) {
-                        lost |= !lds_update<MM, SORTED>(
-                            P, lkey, lsum, lcnt, lmin, lmax, ne, s0, v0 + v1,
+                        lost |= !lds_update<MM>(
+                            lkey, lsum, lcnt, lmin, lmax, ne, s0, v0 + v1,
                             2u, fmin(v0, v1), fmax(v0, v1), iA, preA);
                     } else {
                         if (a0)
-                            lost |= !lds_update<MM, SORTED>(
-                                P, lkey, lsum, lcnt, lmin, lmax, ne, s0, v0,
+                            lost |= !lds_update<MM>(
+                                lkey, lsum, lcnt, lmin, lmax, ne, s0, v0,
                                 1u, v0, v0, iA, preA);
                         if (a1)
-                            lost |= !lds_update<MM, SORTED>(
-                                P, lkey, lsum, lcnt, lmin, lmax, ne, s1, v1,
+                            lost |= !lds_update<MM>(
+                                lkey, lsum, lcnt, lmin, lmax, ne, s1, v1,
                                 1u, v1, v1, iB, preB);
                     }
                 }
@@ -933,35 +891,18 @@ k_scan_agg_range2(AggParams P, RangeAux R, RangeOut O) {
                 row = 0;
             }
         }
-        if (SORTED && lost) s_bovf = 1u;
+        if (lost) s_bovf = 1u;
         __syncthreads();
-        if (SORTED) {
-            if (s_bovf) {
-                // more than ne distinct keys in this block's range: the host
-                // re-partitions with more blocks; emit nothing
-                if (threadIdx.x == 0) {
-                    __hip_atomic_fetch_add(O.block_ovf, 1ull, RLX, AGT);
-                    O.desc[blk] = 0ull;
-                }
-            } else {
-                emit_sorted_run<MM>(O, blk, ne, lkey, lsum, lcnt, lmin, lmax,
-                                    lidx, &s_live, &s_empty, &s_off);
+        if (s_bovf) {
+            // more than ne distinct keys in this block's range: the host
+            // re-partitions with more blocks; emit nothing
+            if (threadIdx.x == 0) {
+                __hip_atomic_fetch_add(O.block_ovf, 1ull, RLX, AGT);
+                O.desc[blk] = 0ull;
             }
         } else {
-            unsigned long long live = 0;
-            for (uint32_t i = threadIdx.x; i < ne; i += blockDim.x) {
-                if (lkey[i] == KEY_EMPTY) continue;
-                live++;
-                agg_update(P, lkey[i], 0, lsum[i],
-                           (unsigned long long)lcnt[i],
-                           MM ? ordered_f64(lmin[i]) : 0.0,
-                           MM ? ordered_f64(lmax[i]) : 0.0, 0xFFFFFFFFu, 0,
-                           false);
-            }
-            for (int off = 32; off > 0; off >>= 1)
-                live += __shfl_down(live, off, 64);
-            if ((threadIdx.x & 63) == 0 && live)
-                __hip_atomic_fetch_add(P.fill, live, RLX, AGT);
+            emit_sorted_run<MM>(O, blk, ne, lkey, lsum, lcnt, lmin, lmax,
+                                lidx, &s_live, &s_empty, &s_off);
         }
         __syncthreads();
     }
@@ -2618,34 +2559,30 @@ hipError_t launch_range_bounds(hipStream_t s, const AggParams& p,
     return hipGetLastError();
 }
 
-template <bool MM, bool SORTED>
+template <bool MM>
 static hipError_t launch_range2_inst(hipStream_t s, const AggParams& p,
                                      const RangeAux& r, const RangeOut& o) {
-    // per slot: key 8 + sum 8 + cnt 4 [+ min 8 + max 8] [+ sort index 2]
-    const size_t lds = (size_t)r.ne * ((MM ? 36 : 20) + (SORTED ? 2 : 0));
+    // per slot: key 8 + sum 8 + cnt 4 [+ min 8 + max 8] + sort index 2
+    const size_t lds = (size_t)r.ne * (MM ? 38 : 22);
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(
-            reinterpret_cast<const void*>(&k_scan_agg_range2<MM, SORTED>),
+            reinterpret_cast<const void*>(&k_scan_agg_range2<MM>),
             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((k_scan_agg_range2<MM, SORTED>), dim3(r.n_blocks),
-                       dim3(256), lds, s, p, r, o);
+    hipLaunchKernelGGL(k_scan_agg_range2<MM>, dim3(r.n_blocks), dim3(256),
+                       lds, s, p, r, o);
     return hipGetLastError();
 }
 
 hipError_t launch_scan_agg_range2(hipStream_t s, const AggParams& p,
                                   const RangeAux& r, bool minmax,
-                                  const RangeOut* sorted) {
+                                  const RangeOut& out) {
     // the sort permutation is u16 and the slot mask needs a power of two
     if (r.ne == 0 || (r.ne & (r.ne - 1)) || r.ne > 32768u)
         return hipErrorInvalidValue;
-    if (sorted)
-        return minmax ? launch_range2_inst<true, true>(s, p, r, *sorted)
-                      : launch_range2_inst<false, true>(s, p, r, *sorted);
-    const RangeOut none{};
-    return minmax ? launch_range2_inst<true, false>(s, p, r, none)
-                  : launch_range2_inst<false, false>(s, p, r, none);
+    return minmax ? launch_range2_inst<true>(s, p, r, out)
+                  : launch_range2_inst<false>(s, p, r, out);
 }
 
 hipError_t launch_place_runs(hipStream_t s, const RangePlace& q) {

@@ -101,16 +101,13 @@ def test_plain_parity(ds_plain, ops, rng):
     assert len(res["series_id"]) == 2_000
 
 
-def test_old_route_switch(ds_plain):
-    # HX_RANGE_SORTED=0: the range kernel flushes into the global table and
-    # the result goes through compaction + sort + gather, as before
+def test_table_route_same_queries(ds_plain):
+    # HX_RANGE=0: series-only grouping on the global-table route (wave
+    # kernel, compaction, sort, gather) answers the same queries
     out, m = ds_plain
-    os.environ["HX_RANGE_SORTED"] = "0"
-    try:
+    with _env(HX_RANGE="0"):
         check(out, FULL, SUM_COUNT)
         check(out, middle_range(m), OPS_ALL)
-    finally:
-        del os.environ["HX_RANGE_SORTED"]
 
 
 # ---- key order --------------------------------------------------------------
@@ -195,6 +192,26 @@ def test_block_overflow_retries_exhausted(ds_wide, capfd):
                      err), err
     assert "kernel=wave" in err, err
     assert len(res["series_id"]) == 100_000
+
+
+def test_gave_up_plan_stays_on_table_route(ds_wide, capfd):
+    # one prepared, two execs: the first runs out of re-partitioning retries
+    # (as above) and finishes on the wave kernel; the second must go to the
+    # wave kernel directly, without another range launch
+    from horaedb_amd import Store
+    out, m = ds_wide
+    exp = _expected(out, FULL, OPS_ALL)
+    with _env(HX_RANGE_TARGET="1000000000", HX_RANGE_NE="16", HX_DEBUG="1"):
+        with Store(out) as st, st.prepare(FULL, devices=[0]) as pr:
+            first = pr.exec_agg(ops=OPS_ALL)
+            err1 = capfd.readouterr().err
+            second = pr.exec_agg(ops=OPS_ALL)
+            err2 = capfd.readouterr().err
+    _compare(first, exp, OPS_ALL)
+    _compare(second, exp, OPS_ALL)
+    assert "kernel=range-sorted" in err1 and "kernel=wave" in err1, err1
+    assert "kernel=wave" in err2, err2
+    assert "kernel=range-sorted" not in err2, err2
 
 
 def test_staging_overflow_retry(ds_plain, capfd):
