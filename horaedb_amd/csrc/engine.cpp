@@ -29,6 +29,7 @@
 #include "hx_kernels.h"
 #include "hx_internal.h"
 #include "snappy_stored.h"
+#include "def_levels.h"
 
 // ---------------------------------------------------------------------------
 // Zstd page codec (config.rs:84 includes Zstd): decompressed on the HOST at
@@ -347,12 +348,14 @@ namespace {
 struct DevPlan {
     int device = 0;
     std::vector<hx::RgDesc> rgs;
+    std::vector<hx::RgValid> rg_valid;   // parallel to rgs; has_nulls only
     std::vector<hx::SstDev> ssts;
     std::vector<hx::ClusterDev> clusters;
     std::vector<int32_t> cluster_members;
     std::vector<hx::DeltaPageDesc> delta_pages;
     std::vector<hx::BaPageDesc> ba_pages;   // byte-value stores: handle walk
     std::vector<hx::SnappyPageDesc> snappy_pages;
+    std::vector<hx::ExpandPageDesc> expand_pages;  // OPTIONAL PLAIN bodies
     std::vector<hx::RleDictPageDesc> rledict_pages;
     std::vector<hx::CopyDesc> copies;
     size_t blob_bytes = 0;
@@ -361,6 +364,9 @@ struct DevPlan {
     // stored Snappy pages read in place from the blob (hx_get_decode_stats)
     uint64_t pages_in_place = 0;
     uint64_t bytes_in_place = 0;
+    // a value page with real nulls was staged: its validity bitmap is in the
+    // blob and the null-aware kernel instances run
+    bool has_nulls = false;
 
     // host staging
     uint8_t* h_blob = nullptr;
@@ -376,6 +382,7 @@ struct DevPlan {
     hx::DeltaPageDesc* d_delta = nullptr;
     hx::BaPageDesc* d_ba = nullptr;
     hx::SnappyPageDesc* d_snappy = nullptr;
+    hx::ExpandPageDesc* d_expand = nullptr;
     hx::RleDictPageDesc* d_rledict = nullptr;
     hx::CopyDesc* d_copies = nullptr;
 
@@ -468,6 +475,63 @@ static int hip_device_count() {
 
 static size_t align64(size_t x) { return (x + 63) & ~size_t(63); }
 
+// Definition levels of one data page of an OPTIONAL column, read from the
+// place that holds them: a v2 page keeps them outside the
+// compressed region (page[0, def_level_bytes)); an uncompressed v1 page opens
+// with the length-prefixed block (walk_pages sized it); a compressed v1 page
+// has the block inside the stream — a Snappy stream gives it up through a
+// prefix decode, a Zstd page after the host decompress (`post`, the whole
+// decompressed body; unused otherwise). `page` is the page's bytes as stored.
+// *in_stream receives the block's size inside the decompressed body (0 when
+// def_level_bytes already accounts for it). bitmap may be null. Returns an
+// empty string, or what is wrong with the page.
+static std::string page_levels(const hx::PageDesc& dp, int32_t codec,
+                               const uint8_t* page, const uint8_t* post,
+                               size_t post_len, uint64_t* bitmap,
+                               uint32_t* in_stream, uint32_t* n_valid) {
+    *in_stream = 0;
+    const uint8_t* lv = nullptr;
+    size_t lv_len = 0;
+    std::vector<uint8_t> pre;
+    if (!dp.levels_in_stream) {
+        const size_t skip = dp.page_type == 0 ? 4 : 0;  // v1 length prefix
+        if (size_t(dp.def_level_bytes) < skip) return "level block truncated";
+        lv = page + skip;
+        lv_len = size_t(dp.def_level_bytes) - skip;
+    } else if (codec == hx::CODEC_SNAPPY) {
+        uint8_t head[4];
+        if (hx_snappy_prefix(page, size_t(dp.compressed_size), head, 4) != 4)
+            return "Snappy page too short for its level block";
+        // framing against the declared page size; the prefix decode below
+        // fails if the stream is shorter than that
+        const uint64_t rle = uint64_t(head[0]) | uint64_t(head[1]) << 8 |
+                             uint64_t(head[2]) << 16 | uint64_t(head[3]) << 24;
+        if (4 + rle > uint64_t(dp.uncompressed_size))
+            return "v1 def-level block exceeds page";
+        const uint32_t bb = uint32_t(4 + rle);
+        pre.resize(bb);
+        if (hx_snappy_prefix(page, size_t(dp.compressed_size), pre.data(),
+                             bb) != long(bb))
+            return "Snappy stream ends inside the level block";
+        lv = pre.data() + 4;
+        lv_len = bb - 4;
+        *in_stream = bb;
+    } else {
+        uint32_t bb = 0;
+        if (!post || hx_level_block_bytes(post, post_len, &bb) != HX_LVL_OK)
+            return "v1 def-level block exceeds page";
+        lv = post + 4;
+        lv_len = bb - 4;
+        *in_stream = bb;
+    }
+    if (dp.num_values < 0) return "negative value count";
+    const int rc = hx_levels_to_bitmap(lv, lv_len, uint32_t(dp.num_values),
+                                       bitmap, n_valid);
+    if (rc != HX_LVL_OK)
+        return "malformed definition levels (code " + std::to_string(rc) + ")";
+    return std::string();
+}
+
 static hx_status stage_device(hx_prepared* P, DevPlan& plan,
                               std::vector<StagedSst*>& members) {
     const bool bytes_val = P->h->bytes_value;
@@ -481,6 +545,9 @@ static hx_status stage_device(hx_prepared* P, DevPlan& plan,
         int32_t codec;
         bool required;
         size_t dst_off;     // blob offset reserved (chunk_size upper bound)
+        size_t bitmap_off = 0;  // OPTIONAL value column: blob offset reserved
+                                // for the page's validity words (64-aligned)
+        bool has_nulls = false; // filled after page walk: the words are live
         // filled after page walk:
         uint64_t final_off = 0;  // RgDesc offset value (blob or OFF_DEC)
     };
@@ -555,6 +622,12 @@ static hx_status stage_device(hx_prepared* P, DevPlan& plan,
                 // body lands 64-byte aligned (pad <= 63, see the page walk)
                 if (cr.codec == hx::CODEC_SNAPPY) reserve += 64;
                 blob_off = align64(blob_off + reserve);
+                if (c == 2 && !cr.required && !bytes_val &&
+                    cr.num_values > 0) {
+                    j.bitmap_off = blob_off;
+                    blob_off = align64(blob_off +
+                                       (size_t(cr.num_values) + 63) / 64 * 8);
+                }
                 jobs.push_back(j);
             }
             row_base += rg.n_rows;
@@ -681,6 +754,50 @@ static hx_status stage_device(hx_prepared* P, DevPlan& plan,
             const uint8_t* src = tmp.data() + in_chunk + dp->def_level_bytes;
             uint64_t data_off = j.dst_off;  // raw page bytes (post-codec)
             size_t raw_size = payload;
+            // OPTIONAL column: the levels are decoded, never trusted to the
+            // statistics. lvl = level bytes that open the DEcompressed body
+            // of a compressed v1 page (0 otherwise: def_level_bytes already
+            // skipped them). Zstd pages are looked at after the decompress.
+            static const char* const col_names[4] = {"series_id", "timestamp",
+                                                     "value", "__seq__"};
+            uint32_t lvl = 0;
+            uint32_t n_valid = (uint32_t)j.num_values;
+            auto check_levels = [&](const uint8_t* post, size_t post_len) {
+                std::string why = page_levels(
+                    *dp, j.codec, tmp.data() + in_chunk, post, post_len,
+                    j.bitmap_off ? (uint64_t*)(plan.h_blob + j.bitmap_off)
+                                 : nullptr,
+                    &lvl, &n_valid);
+                if (why.empty() && int64_t(n_valid) != j.num_values) {
+                    const std::string n_null =
+                        std::to_string(j.num_values - int64_t(n_valid)) +
+                        " null(s): ";
+                    if (j.col != 2)
+                        why = n_null + "nulls in a key column are not "
+                                       "supported";
+                    else if (bytes_val)
+                        why = n_null + "nulls in a Binary value column are "
+                                       "not supported";
+                    else if (P->h->update_mode == 1)
+                        why = n_null + "Append mode over null values is not "
+                                       "supported";
+                    else if (dp->encoding != hx::ENC_PLAIN)
+                        why = n_null + "nulls in a dictionary-encoded value "
+                                       "page are not supported (PLAIN only)";
+                    else
+                        j.has_nulls = true;
+                }
+                if (why.empty()) return true;
+                std::lock_guard<std::mutex> g(mu);
+                err_msg = j.ss->cat->path + ": column " + col_names[j.col] +
+                          ": " + why;
+                err_flag = 1;
+                return false;
+            };
+            const bool zstd_page = j.codec == hx::CODEC_ZSTD && dp->is_compressed;
+            if (!j.required && !(zstd_page && dp->levels_in_stream) &&
+                !check_levels(nullptr, 0))
+                break;
             if (j.codec == hx::CODEC_ZSTD && dp->is_compressed) {
                 // host-side decompress into the blob (staging, untimed)
                 size_t want = size_t(dp->uncompressed_size) -
@@ -694,6 +811,15 @@ static hx_status stage_device(hx_prepared* P, DevPlan& plan,
                     break;
                 }
                 raw_size = want;
+                if (!j.required && dp->levels_in_stream) {
+                    // drop the level block: the body moves to the reserved
+                    // (64-aligned) start, as for a REQUIRED page
+                    if (!check_levels(plan.h_blob + j.dst_off, want)) break;
+                    std::memmove(plan.h_blob + j.dst_off,
+                                 plan.h_blob + j.dst_off + lvl, want - lvl);
+                    raw_size = want - lvl;
+                    lvl = 0;
+                }
             }
             // Stored Snappy page (preamble + ONE literal covering the whole
             // page — what the writer emits for incompressible data): nothing
@@ -712,20 +838,29 @@ static hx_status stage_device(hx_prepared* P, DevPlan& plan,
                                size_t(dp->def_level_bytes));
                 uint32_t body_off = 0;
                 if (hx_snappy_stored_literal(src, payload, ulen, &body_off)) {
+                    // an OPTIONAL v1 page's literal opens with the level
+                    // block (lvl <= ulen, checked against the page size):
+                    // the PLAIN body behind it is what gets aligned
+                    body_off += lvl;
                     const size_t pad = (64 - (body_off & 63u)) & 63u;
                     // reserve = comp_size + 64 >= pad + payload
                     std::memcpy(plan.h_blob + j.dst_off + pad, src, payload);
                     data_off = j.dst_off + pad + body_off;
-                    raw_size = ulen;
+                    raw_size = ulen - lvl;
+                    lvl = 0;
                     stored = true;
                     std::lock_guard<std::mutex> g(mu);
                     plan.pages_in_place++;
-                    plan.bytes_in_place += ulen;
+                    plan.bytes_in_place += raw_size;
                 }
             }
             if (!stored && !(j.codec == hx::CODEC_ZSTD && dp->is_compressed))
                 std::memcpy(plan.h_blob + j.dst_off, src, payload);
-            if (!stored && j.codec == hx::CODEC_SNAPPY && dp->is_compressed) {
+            if (!stored && j.codec == hx::CODEC_SNAPPY && dp->is_compressed &&
+                dp->uncompressed_size == dp->def_level_bytes) {
+                raw_size = 0;   // v2 page of nulls only: nothing to decode
+            } else if (!stored && j.codec == hx::CODEC_SNAPPY &&
+                       dp->is_compressed) {
                 std::lock_guard<std::mutex> g(mu);
                 hx::SnappyPageDesc sp{};
                 sp.src_off = j.dst_off;
@@ -735,8 +870,10 @@ static hx_status stage_device(hx_prepared* P, DevPlan& plan,
                 sp.dst_off = hx::OFF_DEC | dec_off;
                 dec_off = align64(dec_off + sp.uncomp_len);
                 plan.snappy_pages.push_back(sp);
-                data_off = sp.dst_off;
-                raw_size = sp.uncomp_len;
+                // the decoder's dst stays 64-aligned; an OPTIONAL v1 page's
+                // body follows its level block there
+                data_off = sp.dst_off + lvl;
+                raw_size = sp.uncomp_len - lvl;
             }
 
             if (bytes_val && j.col == 2) {
@@ -765,11 +902,30 @@ static hx_status stage_device(hx_prepared* P, DevPlan& plan,
                 j.final_off = hx::OFF_DEC |
                               (j.ss->bytes_handles + uint64_t(j.row_base) * 8);
             } else if (dp->encoding == hx::ENC_PLAIN) {
-                if (raw_size != size_t(j.num_values) * 8) {
+                // the body holds the present values only
+                if (raw_size != size_t(n_valid) * 8) {
                     std::lock_guard<std::mutex> g(mu);
                     err_msg = j.ss->cat->path + ": PLAIN payload size mismatch";
                     err_flag = 1;
                     break;
+                }
+                if (lvl || j.has_nulls) {
+                    // body behind a level block in dec (not 8-aligned), or
+                    // packed around nulls: k_expand_optional writes the dense
+                    // column on every decode pass
+                    std::lock_guard<std::mutex> g(mu);
+                    hx::ExpandPageDesc ep{};
+                    ep.src_off = data_off - lvl;
+                    ep.src_len = (uint32_t)(raw_size + lvl);
+                    ep.lvl_bytes = lvl;
+                    ep.n_rows = (uint32_t)j.num_values;
+                    ep.n_valid = n_valid;
+                    ep.bitmap_off = j.has_nulls ? j.bitmap_off : 0;
+                    ep.dst_off = hx::OFF_DEC | dec_off;
+                    dec_off = align64(dec_off + size_t(j.num_values) * 8);
+                    plan.expand_pages.push_back(ep);
+                    if (j.has_nulls) plan.has_nulls = true;
+                    data_off = ep.dst_off;
                 }
                 j.final_off = data_off;
             } else if (dp->encoding == hx::ENC_DELTA_BINARY_PACKED && j.col != 2) {
@@ -802,7 +958,9 @@ static hx_status stage_device(hx_prepared* P, DevPlan& plan,
                                           j.codec == hx::CODEC_ZSTD
                                               ? size_t(j.uncomp_size)
                                               : size_t(0));
-                size_t dict_dst = j.dst_off + ((raw_size + 15) & ~size_t(15));
+                size_t dict_dst = j.dst_off +
+                                  ((std::max(raw_size, payload) + 15) &
+                                   ~size_t(15));
                 size_t dict_need = j.codec == hx::CODEC_ZSTD
                                        ? size_t(dictp->uncompressed_size)
                                        : dict_payload;
@@ -872,6 +1030,7 @@ static hx_status stage_device(hx_prepared* P, DevPlan& plan,
     if (err_flag.load()) return fail(HX_ERR_UNSUPPORTED, err_msg);
 
     // patch RgDesc offsets from job results; build dense copies for overlap
+    plan.rg_valid.assign(plan.rgs.size(), hx::RgValid{0, 0});
     size_t job_i = 0;
     size_t rg_i = 0;
     for (StagedSst* ss : members) {
@@ -881,8 +1040,11 @@ static hx_status stage_device(hx_prepared* P, DevPlan& plan,
         for (size_t k = 0; k < ss->rg_idx.size(); k++, rg_i++) {
             hx::RgDesc& rd = plan.rgs[rg_i];
             uint64_t offs[4] = {0, 0, 0, 0};
-            for (int c = 0; c < n_staged_cols; c++, job_i++)
+            for (int c = 0; c < n_staged_cols; c++, job_i++) {
                 offs[c] = jobs[job_i].final_off;
+                if (c == 2 && jobs[job_i].has_nulls)
+                    plan.rg_valid[rg_i].off = jobs[job_i].bitmap_off;
+            }
             rd.series_off = offs[0];
             rd.ts_off = offs[1];
             rd.val_off = offs[2];
@@ -928,6 +1090,7 @@ static hx_status stage_device(hx_prepared* P, DevPlan& plan,
         if (split < 1) split = 1;
         const size_t n_old = plan.rgs.size();
         std::vector<hx::RgDesc> sliced;
+        std::vector<hx::RgValid> sliced_valid;
         std::vector<int32_t> new_first(n_old);
         std::vector<int32_t> last_slice(n_old);
         for (size_t i = 0; i < n_old; i++) {
@@ -942,6 +1105,8 @@ static hx_status stage_device(hx_prepared* P, DevPlan& plan,
                 sl.val_off = rd.val_off + uint64_t(start) * 8;
                 sl.n_rows = std::min(ssize, rd.n_rows - start);
                 sl.row_base = rd.row_base + start;
+                // same bitmap, later bit: a slice need not start on a word
+                sliced_valid.push_back({plan.rg_valid[i].off, start});
                 sl.next_rg = (start + ssize < rd.n_rows)
                                  ? (int32_t)sliced.size() + 1
                                  : rd.next_rg;  // old id; remapped below
@@ -976,12 +1141,16 @@ static hx_status stage_device(hx_prepared* P, DevPlan& plan,
         std::vector<int32_t> inv(sliced.size());
         for (size_t i = 0; i < sliced.size(); i++) inv[order[i]] = (int32_t)i;
         std::vector<hx::RgDesc> reordered(sliced.size());
+        std::vector<hx::RgValid> reordered_valid(sliced.size());
         for (size_t i = 0; i < sliced.size(); i++) {
             reordered[i] = sliced[order[i]];
+            reordered_valid[i] = sliced_valid[order[i]];
             if (reordered[i].next_rg >= 0)
                 reordered[i].next_rg = inv[reordered[i].next_rg];
         }
         plan.rgs.swap(reordered);
+        plan.rg_valid.swap(reordered_valid);
+        if (!plan.has_nulls) plan.rg_valid.clear();   // nothing to upload
     }
 
     // per-SST rg lists in row order (series-range kernel): the
@@ -1025,13 +1194,26 @@ static hx_status stage_device(hx_prepared* P, DevPlan& plan,
         return hipMemcpyAsync(dptr, vec.data(), vec.size() * sizeof(T),
                               hipMemcpyHostToDevice, plan.stream);
     };
-    HIP_TRY(upload(plan.d_rgs, plan.rgs));
+    if (plan.has_nulls && !plan.rgs.empty()) {
+        // the RgValid entries ride behind the RgDesc array (hx_device.h)
+        const size_t rg_bytes = plan.rgs.size() * sizeof(hx::RgDesc);
+        const size_t rv_bytes = plan.rg_valid.size() * sizeof(hx::RgValid);
+        HIP_TRY(hipMalloc((void**)&plan.d_rgs, rg_bytes + rv_bytes));
+        HIP_TRY(hipMemcpyAsync(plan.d_rgs, plan.rgs.data(), rg_bytes,
+                               hipMemcpyHostToDevice, plan.stream));
+        HIP_TRY(hipMemcpyAsync((uint8_t*)plan.d_rgs + rg_bytes,
+                               plan.rg_valid.data(), rv_bytes,
+                               hipMemcpyHostToDevice, plan.stream));
+    } else {
+        HIP_TRY(upload(plan.d_rgs, plan.rgs));
+    }
     HIP_TRY(upload(plan.d_ssts, plan.ssts));
     HIP_TRY(upload(plan.d_clusters, plan.clusters));
     HIP_TRY(upload(plan.d_members, plan.cluster_members));
     HIP_TRY(upload(plan.d_delta, plan.delta_pages));
     HIP_TRY(upload(plan.d_ba, plan.ba_pages));
     HIP_TRY(upload(plan.d_snappy, plan.snappy_pages));
+    HIP_TRY(upload(plan.d_expand, plan.expand_pages));
     HIP_TRY(upload(plan.d_rledict, plan.rledict_pages));
     HIP_TRY(upload(plan.d_copies, plan.copies));
     HIP_TRY(upload(plan.d_sst_rgs, plan.h_sst_rgs));
@@ -1239,7 +1421,8 @@ extern "C" void hx_prepared_free(hx_prepared* P) {
                         (void*)plan.d_ssts, (void*)plan.d_clusters,
                         (void*)plan.d_members, (void*)plan.d_delta,
                         (void*)plan.d_ba,
-                        (void*)plan.d_snappy, (void*)plan.d_rledict,
+                        (void*)plan.d_snappy, (void*)plan.d_expand,
+                        (void*)plan.d_rledict,
                         (void*)plan.d_copies, (void*)plan.t_slab,
                         (void*)plan.t_bstore, (void*)plan.d_counters,
                         (void*)plan.d_sset, (void*)plan.d_sst_rgs,
@@ -1386,6 +1569,12 @@ hx_status ensure_decoded(DevPlan& plan, hipStream_t s) {
         HIP_TRY(hx::launch_snappy(s, plan.d_blob, plan.d_dec, plan.d_snappy,
                                   (uint32_t)plan.snappy_pages.size(),
                                   plan.d_counters + 1));
+    if (!plan.expand_pages.empty())
+        // after the Snappy decode: its output is this kernel's source
+        HIP_TRY(hx::launch_expand_optional(s, plan.d_blob, plan.d_dec,
+                                           plan.d_expand,
+                                           (uint32_t)plan.expand_pages.size(),
+                                           plan.d_counters + 1));
     if (!plan.rledict_pages.empty())
         HIP_TRY(hx::launch_rledict(s, plan.d_blob, plan.d_dec, plan.d_rledict,
                                    (uint32_t)plan.rledict_pages.size(),
@@ -1415,7 +1604,8 @@ hx_status ensure_decoded(DevPlan& plan, hipStream_t s) {
                       hipMemcpyDeviceToHost));
     if (decode_err)
         return fail(HX_ERR_FORMAT, "page decode failed (malformed snappy "
-                                   "stream or delta page)");
+                                   "stream, delta page or OPTIONAL page "
+                                   "body)");
     plan.decoded = true;
     return HX_OK;
 }
@@ -1681,7 +1871,8 @@ static hx_status exec_range_sorted(hx_prepared* P, DevPlan& plan,
         if (est != HX_OK) return est;
         hipEvent_t e0 = plan.ev[0], e1 = plan.ev[1];
         HIP_TRY(hipEventRecord(e0, s));
-        hipError_t ke = hx::launch_scan_agg_range2(s, A, R, mm, O);
+        hipError_t ke = hx::launch_scan_agg_range2(s, A, R, mm,
+                                                   plan.has_nulls, O);
         if (ke != hipSuccess)
             return fail(HX_ERR_HIP,
                         std::string("range kernel launch failed: ") +
@@ -1874,7 +2065,7 @@ static hx_status exec_table(hx_prepared* P, DevPlan& plan,
         if (est != HX_OK) return est;
         hipEvent_t e0 = plan.ev[0], e1 = plan.ev[1];
         HIP_TRY(hipEventRecord(e0, s));
-        HIP_TRY(hx::launch_scan_agg(s, A, 0));
+        HIP_TRY(hx::launch_scan_agg(s, A, 0, plan.has_nulls));
         HIP_TRY(hipEventRecord(e1, s));
         HIP_TRY(hipStreamSynchronize(s));
         float ms = 0;
@@ -2242,6 +2433,91 @@ extern "C" hx_status hx_get_decode_stats(hx_prepared* P, hx_decode_stats* out) {
     return HX_OK;
 }
 
+extern "C" hx_status hx_debug_page_levels(
+    const char* path, int32_t row_group, const char* column,
+    uint64_t* bitmap_out, uint64_t cap_words, int64_t* n_rows,
+    int64_t* n_valid, int32_t* level_bytes) {
+    if (!path || !column || !n_rows || !n_valid || !level_bytes)
+        return fail(HX_ERR_INVALID, "null argument");
+    static const char* const names[4] = {"series_id", "timestamp", "value",
+                                         "__seq__"};
+    int col = -1;
+    for (int k = 0; k < 4; k++)
+        if (std::strcmp(column, names[k]) == 0) col = k;
+    if (col < 0)
+        return fail(HX_ERR_INVALID, std::string("column ") + column +
+                                        " is not one staging reads");
+    CatSst cat;
+    hx_status st = read_file_meta(path, 0, cat);
+    if (st != HX_OK) return st;
+    if (row_group < 0 || size_t(row_group) >= cat.rgs.size())
+        return fail(HX_ERR_INVALID, "row group out of range");
+    const ChunkRef& cr = cat.rgs[row_group].cols[col];
+    if (cr.comp_size <= 0 || cr.comp_size > (int64_t)1 << 31)
+        return fail(HX_ERR_FORMAT, cat.path + ": implausible chunk size");
+    std::vector<uint8_t> tmp(cr.comp_size);
+    int fd = open(path, O_RDONLY);
+    if (fd < 0) return fail(HX_ERR_IO, "open " + cat.path);
+    const ssize_t got = pread(fd, tmp.data(), tmp.size(), cr.chunk_start);
+    close(fd);
+    if (got != (ssize_t)tmp.size())
+        return fail(HX_ERR_IO, "chunk read " + cat.path);
+    std::vector<hx::PageDesc> pages;
+    try {
+        pages = hx::walk_pages(tmp.data(), tmp.size(), cr.chunk_start,
+                               cr.num_values, !cr.required, cr.codec);
+    } catch (const std::exception& e) {
+        return fail(HX_ERR_FORMAT, cat.path + ": " + e.what());
+    }
+    const hx::PageDesc* dp = nullptr;
+    int n_data = 0;
+    for (const auto& p : pages)
+        if (p.page_type == 0 || p.page_type == 3) {
+            dp = &p;
+            n_data++;
+        }
+    if (n_data != 1 || dp->num_values != cr.num_values || dp->num_values < 0)
+        return fail(HX_ERR_UNSUPPORTED,
+                    cat.path + ": expected one data page per chunk");
+    const size_t words = (size_t(dp->num_values) + 63) / 64;
+    if (bitmap_out && cap_words < words)
+        return fail(HX_ERR_INVALID, "bitmap capacity too small");
+    *n_rows = dp->num_values;
+    if (cr.required) {
+        *n_valid = dp->num_values;
+        *level_bytes = 0;
+        if (bitmap_out) {
+            for (size_t i = 0; i < words; i++) bitmap_out[i] = 0;
+            hx_bitmap_set_range(bitmap_out, 0, uint64_t(dp->num_values));
+        }
+        return HX_OK;
+    }
+    const uint8_t* page = tmp.data() + size_t(dp->payload_off - cr.chunk_start);
+    std::vector<uint8_t> post;
+    if (dp->levels_in_stream && cr.codec == hx::CODEC_ZSTD) {
+        if (!zstd().ok)
+            return fail(HX_ERR_UNSUPPORTED, cat.path + ": Zstd pages but "
+                                            "libzstd.so.1 is not loadable");
+        post.resize(size_t(dp->uncompressed_size));
+        const size_t n = zstd().decompress(post.data(), post.size(), page,
+                                           size_t(dp->compressed_size));
+        if (zstd().is_error(n) || n != post.size())
+            return fail(HX_ERR_FORMAT, cat.path + ": Zstd page decode failed");
+    } else if (dp->levels_in_stream && cr.codec != hx::CODEC_SNAPPY) {
+        return fail(HX_ERR_UNSUPPORTED, cat.path + ": codec unsupported "
+                                        "(uncompressed, Snappy and Zstd)");
+    }
+    uint32_t in_stream = 0, nv = 0;
+    const std::string why =
+        page_levels(*dp, cr.codec, page, post.empty() ? nullptr : post.data(),
+                    post.size(), bitmap_out, &in_stream, &nv);
+    if (!why.empty())
+        return fail(HX_ERR_FORMAT, cat.path + ": column " + column + ": " + why);
+    *n_valid = nv;
+    *level_bytes = int32_t(in_stream ? in_stream : dp->def_level_bytes);
+    return HX_OK;
+}
+
 extern "C" hx_status hx_debug_snappy_decompress(
     const uint8_t* streams, const uint64_t* offs, const uint32_t* comp_lens,
     const uint32_t* uncomp_lens, uint32_t n, uint8_t* out,
@@ -2356,7 +2632,9 @@ extern "C" hx_status hx_scan(hx_handle* h, const hx_scan_spec* spec,
         return fail(HX_ERR_UNSUPPORTED,
                     "row streams above 2^32 rows per call: split the range");
     // device buffers: 3-4 columns + sort keys/scratch + 3 perms
-    size_t need = cap * 8 * (append ? 6 : 5) + cap * 4 * 3 + 64;
+    const bool nulls = plan.has_nulls;   // never with append / Binary values
+    size_t need = cap * 8 * ((append ? 6 : 5) + (nulls ? 1 : 0)) +
+                  cap * 4 * 3 + 64;
     st = ensure_dev(&plan.d_scratch, &plan.scratch_cap, need);
     if (st != HX_OK) return st;
     uint8_t* base = (uint8_t*)plan.d_scratch;
@@ -2369,6 +2647,8 @@ extern "C" hx_status hx_scan(hx_handle* h, const hx_scan_spec* spec,
     long long* d_ts = (long long*)carve8(cap);
     double* d_val = (double*)carve8(cap);
     uint64_t* d_seq = append ? (uint64_t*)carve8(cap) : nullptr;
+    // one 0/1 word per surviving row: rides the same permutation as value
+    uint64_t* d_valid = nulls ? (uint64_t*)carve8(cap) : nullptr;
     uint64_t* d_keys = (uint64_t*)carve8(cap);
     uint64_t* d_keys_out = (uint64_t*)carve8(cap);
     unsigned long long* d_cursor = (unsigned long long*)carve8(1);
@@ -2387,7 +2667,8 @@ extern "C" hx_status hx_scan(hx_handle* h, const hx_scan_spec* spec,
                             "append stores need file sequences < 2^32");
     }
     HIP_TRY(hx::launch_scan_rows(s, A, 0, A.n_rgs, d_series, d_ts, d_val,
-                                 d_cursor, cap, d_seq, append ? 1 : 0));
+                                 d_cursor, cap, d_seq, append ? 1 : 0,
+                                 d_valid));
     unsigned long long n64 = 0;
     HIP_TRY(hipStreamSynchronize(s));
     HIP_TRY(hipMemcpy(&n64, d_cursor, 8, hipMemcpyDeviceToHost));
@@ -2427,15 +2708,16 @@ extern "C" hx_status hx_scan(hx_handle* h, const hx_scan_spec* spec,
     const uint32_t* perm = perm_a;
 
     // gather the three columns by the final permutation, one D2H
-    const unsigned long long* srcs[3] = {
+    const unsigned long long* srcs[4] = {
         (const unsigned long long*)d_series, (const unsigned long long*)d_ts,
-        (const unsigned long long*)d_val};
+        (const unsigned long long*)d_val, (const unsigned long long*)d_valid};
+    const uint32_t n_src = nulls ? 4 : 3;
     // reuse keys buffers as gather dst (need 3n; keys has 2n) — allocate
-    std::vector<uint64_t> host(3 * size_t(n));
+    std::vector<uint64_t> host(n_src * size_t(n));
     unsigned long long* d_dst = nullptr;
-    HIP_TRY(hipMalloc((void**)&d_dst, 3 * size_t(n) * 8));
-    HIP_TRY(hx::launch_gather_multi(s, srcs, 3, perm, d_dst, n));
-    HIP_TRY(hipMemcpyAsync(host.data(), d_dst, 3 * size_t(n) * 8,
+    HIP_TRY(hipMalloc((void**)&d_dst, n_src * size_t(n) * 8));
+    HIP_TRY(hx::launch_gather_multi(s, srcs, n_src, perm, d_dst, n));
+    HIP_TRY(hipMemcpyAsync(host.data(), d_dst, n_src * size_t(n) * 8,
                            hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
 
@@ -2525,8 +2807,20 @@ extern "C" hx_status hx_scan(hx_handle* h, const hx_scan_spec* spec,
     std::vector<int32_t> coltypes(proj.size());
     std::vector<int64_t> rebased;
     for (size_t i = 0; i < proj.size(); i++) coltypes[i] = kTypes[proj[i]];
+    // validity: one bitmap per batch for the value column, NULL pointers for
+    // the key columns; no array at all for a plan without nulls
+    std::vector<uint8_t> vbits;
+    std::vector<const uint8_t*> validity(proj.size(), nullptr);
     for (uint32_t off = 0; off < n_out_rows; off += BATCH) {
         uint32_t len = std::min(BATCH, n_out_rows - off);
+        if (nulls) {
+            const uint64_t* hv = host.data() + 3 * size_t(n) + off;
+            vbits.assign((len + 7) / 8, 0);
+            for (uint32_t r = 0; r < len; r++)
+                if (hv[r]) vbits[r >> 3] |= uint8_t(1u << (r & 7));
+            for (size_t i = 0; i < proj.size(); i++)
+                validity[i] = proj[i] == 2 ? vbits.data() : nullptr;
+        }
         hx_bytes_col bc{};
         for (size_t i = 0; i < proj.size(); i++) {
             if (proj[i] == 2 && bytesv) {
@@ -2541,7 +2835,8 @@ extern "C" hx_status hx_scan(hx_handle* h, const hx_scan_spec* spec,
                 colptrs[i] = (const void*)(cols_base[proj[i]] + off);
             }
         }
-        hx_col_batch b{len, proj.size(), colptrs.data(), coltypes.data()};
+        hx_col_batch b{len, proj.size(), colptrs.data(), coltypes.data(),
+                       nulls ? validity.data() : nullptr};
         if (cb(ctx, &b)) break;
     }
     return HX_OK;
@@ -2752,6 +3047,12 @@ extern "C" hx_status hx_compact(hx_handle* h, hx_time_range range,
     std::unique_ptr<hx_prepared, void (*)(hx_prepared*)> guard(
         P, hx_prepared_free);
     DevPlan& plan = P->plans[0];
+    // the native writer writes REQUIRED columns: dropping the nulls would be
+    // data loss. Refused before anything is written or unlinked.
+    if (plan.has_nulls)
+        return fail(HX_ERR_UNSUPPORTED,
+                    "compaction inputs hold null values (the native writer "
+                    "writes REQUIRED columns)");
     HIP_TRY(hipSetDevice(plan.device));
     hipStream_t s = plan.stream;
     st = ensure_decoded(plan, s);
@@ -2893,6 +3194,12 @@ extern "C" hx_status hx_compact_files(hx_handle* h,
     std::unique_ptr<hx_prepared, void (*)(hx_prepared*)> guard(
         P, hx_prepared_free);
     DevPlan& plan = P->plans[0];
+    // the native writer writes REQUIRED columns: dropping the nulls would be
+    // data loss. Refused before anything is written or unlinked.
+    if (plan.has_nulls)
+        return fail(HX_ERR_UNSUPPORTED,
+                    "compaction inputs hold null values (the native writer "
+                    "writes REQUIRED columns)");
     HIP_TRY(hipSetDevice(plan.device));
     hipStream_t s = plan.stream;
     st = ensure_decoded(plan, s);

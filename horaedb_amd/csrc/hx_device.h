@@ -29,6 +29,18 @@ struct RgDesc {
     int32_t  _pad;
 };
 
+// Validity of a unit's value column, parallel to the RgDesc array (same
+// index) and present only in plans that staged a null: the n_rgs entries sit
+// in the same device allocation right behind the n_rgs RgDesc
+// ((const RgValid*)(rgs + n_rgs)). Neither RgDesc nor AggParams changed for
+// it, so plans without nulls launch the kernel code they launched before.
+struct RgValid {
+    uint64_t off;          // blob byte offset of the bitmap (LSB-first u64
+                           // words, 1 = value present); 0 = no bitmap, every
+                           // row of the unit has a value
+    uint64_t bit;          // bit of the unit's row 0 within that bitmap
+};
+
 // Per-SST device info. overlap==1 => this SST belongs to a ts-overlap
 // cluster: rows must check higher-seq SSTs of the cluster for
 // equal PKs via binary search over their dense (series, ts) arrays.
@@ -188,6 +200,24 @@ struct SnappyPageDesc {
     uint64_t dst_off;     // dec blob
     uint32_t comp_len;
     uint32_t uncomp_len;
+};
+
+// OPTIONAL-column PLAIN page unit (k_expand_optional, DESIGN §4 kernel 1c).
+// The page's n_valid packed 8-byte values start at src + lvl_bytes: a v1
+// page the Snappy decoder wrote to dec opens with its definition-level block
+// (lvl_bytes = its size, in general not a multiple of 8); every other page
+// was staged without the block (lvl_bytes = 0). The kernel writes a dense
+// n_rows column at dst_off: without a bitmap n_valid == n_rows and it is a
+// realigning copy; with one, row r takes packed[rank(r)] if its bit is set
+// and 0 otherwise.
+struct ExpandPageDesc {
+    uint64_t src_off;     // page bytes (bit63: dec blob), 8-byte aligned
+    uint64_t dst_off;     // dec blob, 64-byte aligned, n_rows * 8 bytes
+    uint64_t bitmap_off;  // blob: (n_rows + 63) / 64 LSB-first words; 0 = none
+    uint32_t src_len;     // bytes at src: lvl_bytes + n_valid * 8 must fit
+    uint32_t lvl_bytes;
+    uint32_t n_rows;
+    uint32_t n_valid;
 };
 
 // Plain copy unit (materialize dense arrays for the overlap path).

@@ -25,3 +25,15 @@ extern "C" hx_status hx_debug_snappy_decompress(
     const uint8_t* streams, const uint64_t* offs, const uint32_t* comp_lens,
     const uint32_t* uncomp_lens, uint32_t n, uint8_t* out,
     const uint64_t* out_offs, uint64_t* n_errors);
+
+// Test hook (exported, not part of the public C-ABI, no GPU needed): run the
+// staging parse of one column chunk — chunk read, page walk, the codec step
+// that exposes the definition levels, levels -> bitmap — and return what
+// staging would use. column is one of series_id, timestamp, value, __seq__.
+// bitmap_out (may be NULL) receives (n_rows + 63) / 64 LSB-first words;
+// cap_words is its capacity. *level_bytes is the size of the level block in
+// front of the page body (0 for a REQUIRED column).
+extern "C" hx_status hx_debug_page_levels(
+    const char* path, int32_t row_group, const char* column,
+    uint64_t* bitmap_out, uint64_t cap_words, int64_t* n_rows,
+    int64_t* n_valid, int32_t* level_bytes);

@@ -25,9 +25,18 @@ hipError_t launch_rledict(hipStream_t s, const uint8_t* blob, uint8_t* dec,
 hipError_t launch_snappy(hipStream_t s, const uint8_t* blob, uint8_t* dec,
                          const SnappyPageDesc* pages, uint32_t n_pages,
                          unsigned long long* err_flag);
+// One workgroup per page; a page whose descriptor does not fit its source
+// (lvl_bytes + n_rows * 8 > src_len) is left unwritten and counted in
+// err_flag.
+hipError_t launch_expand_optional(hipStream_t s, const uint8_t* blob,
+                                  uint8_t* dec, const ExpandPageDesc* pages,
+                                  uint32_t n_pages,
+                                  unsigned long long* err_flag);
 hipError_t launch_copy_u64(hipStream_t s, const uint8_t* blob, uint8_t* dec,
                            const CopyDesc* descs, uint32_t n_descs);
-hipError_t launch_scan_agg(hipStream_t s, const AggParams& p, uint32_t grid);
+// nulls: the plan staged a validity bitmap — launch the null-aware instance
+hipError_t launch_scan_agg(hipStream_t s, const AggParams& p, uint32_t grid,
+                           bool nulls = false);
 // Series-range mode: sample series for quantile boundaries,
 // precompute per-(block,sst) row bounds, then the LDS-table range kernel
 // (k_scan_agg_range2; the name is kept so the profiles/ records match).
@@ -40,7 +49,7 @@ hipError_t launch_range_bounds(hipStream_t s, const AggParams& p,
 // not used); launch_place_runs then assembles the result.
 hipError_t launch_scan_agg_range2(hipStream_t s, const AggParams& p,
                                   const RangeAux& r, bool minmax,
-                                  const RangeOut& out);
+                                  bool nulls, const RangeOut& out);
 // Exclusive scan of the run counts in blk order, then one copy of every run
 // to its final position in the contiguous SoA result (avg computed here).
 hipError_t launch_place_runs(hipStream_t s, const RangePlace& q);
@@ -50,7 +59,8 @@ hipError_t launch_scan_rows(hipStream_t s, const AggParams& p,
                             double* out_value, unsigned long long* cursor,
                             unsigned long long cap,
                             uint64_t* out_seq = nullptr,
-                            int32_t seq_rowidx = 0);
+                            int32_t seq_rowidx = 0,
+                            uint64_t* out_valid = nullptr);
 hipError_t launch_gather_multi(hipStream_t s,
                                const unsigned long long* const* srcs,
                                uint32_t n_arrays, const uint32_t* perm,

@@ -260,6 +260,12 @@ extern "C" hx_status hx_index_query(hx_handle* h, const hx_tag_pred* preds,
                                      path + ": expected one data page per "
                                             "index chunk");
                 }
+                if (dp->null_count > 0) {
+                    close(fd);
+                    return set_error(HX_ERR_FORMAT,
+                                     path + ": index page has nulls "
+                                            "(null_count > 0)");
+                }
                 size_t in_chunk = size_t(dp->payload_off - cc.chunk_start()) +
                                   size_t(dp->def_level_bytes);
                 size_t plen = size_t(dp->compressed_size) -

@@ -293,6 +293,19 @@ __device__ __forceinline__ void agg_update(const AggParams& P, uint64_t s,
     __hip_atomic_fetch_add(P.overflow, 1ull, RLX, AGT);
 }
 
+// Value validity of row r of unit rgi (nullable f64 value column, DESIGN
+// §3): the unit's bitmap is LSB-first in the page blob, its row 0 at bit
+// RgValid::bit. Units without a bitmap (off == 0) hold no nulls. Only the
+// null-aware launches call this; r must be a row of the unit.
+__device__ __forceinline__ bool row_valid(const AggParams& P, uint32_t rgi,
+                                          uint32_t r) {
+    const RgValid rv = ((const RgValid*)(P.rgs + P.n_rgs))[rgi];
+    if (!rv.off) return true;
+    const uint64_t bit = rv.bit + r;
+    const uint64_t w = ((const uint64_t*)(P.blob + rv.off))[bit >> 6];
+    return (w >> (bit & 63u)) & 1ull;
+}
+
 // Per-row filter + dedup (shared by both aggregate kernels).
 // Returns alive; s/t are the row's PK. DESIGN.md §5.
 __device__ __forceinline__ bool row_alive(const AggParams& P, const RgDesc& rg,
@@ -338,8 +351,9 @@ struct WinResult {
     uint64_t hint_k;    // its key value at probe time
 };
 
+template <bool NULLS>
 __device__ __forceinline__ void scan_window(const AggParams& P,
-                                            const RgDesc& rg,
+                                            const RgDesc& rg, uint32_t rgi,
                                             const SstDev& sst,
                                             const uint64_t* S,
                                             const int64_t* T, const double* V,
@@ -388,11 +402,17 @@ __device__ __forceinline__ void scan_window(const AggParams& P,
         if (!alive) v = 0.0;
     }
     int64_t b = (inb && P.bucket_ms) ? floordiv(t, P.bucket_ms) : 0;
+    // a null value is still a row: it counts into matched (and took part in
+    // the dedup above), then drops out of the aggregates
+    if (NULLS && alive) {
+        my_matched += 1ull;
+        alive = row_valid(P, rgi, r);
+    }
     unsigned long long c = alive ? 1ull : 0ull;
     double vv = alive ? v : 0.0;
     double mn = alive ? v : HUGE_VAL;
     double mx = alive ? v : -HUGE_VAL;
-    my_matched += c;
+    if (!NULLS) my_matched += c;
     // issue the table probe NOW: its L3 latency hides under the cross-lane
     // reduction, and a hit skips the dependent probe load in agg_update
     W.hint_i = 0xFFFFFFFFu;
@@ -437,7 +457,8 @@ __device__ __forceinline__ void scan_window(const AggParams& P,
 // dependent table-update chains (L3 probe + atomics) overlap — the kernel
 // is memory-latency-bound (SQ_WAIT_ANY 76%) at full occupancy, so the
 // lever is per-wave memory-level parallelism.
-extern "C" __global__ void __launch_bounds__(256)
+template <bool NULLS>
+__global__ void __launch_bounds__(256)
 k_scan_agg(AggParams P) {
     unsigned long long my_matched = 0;
     const int lane = threadIdx.x & 63;
@@ -470,10 +491,12 @@ k_scan_agg(AggParams P) {
             WinResult A, B;
             B.c = 0;
             B.head = false;
-            scan_window(P, rg, sst, S, T, V, base, n, lane, my_matched, A);
+            scan_window<NULLS>(P, rg, rgi, sst, S, T, V, base, n, lane,
+                               my_matched, A);
             const uint32_t base2 = base + blockDim.x;
             if (base2 < n)
-                scan_window(P, rg, sst, S, T, V, base2, n, lane, my_matched, B);
+                scan_window<NULLS>(P, rg, rgi, sst, S, T, V, base2, n, lane,
+                                   my_matched, B);
             const bool upA = A.head && A.c > 0;
             const bool upB = B.head && B.c > 0;
             if (upA && upB) {  // two independent chains: overlap them
@@ -719,7 +742,7 @@ __device__ __forceinline__ void emit_sorted_run(
     }
 }
 
-template <bool MM>
+template <bool MM, bool NULLS>
 __global__ void __launch_bounds__(256)
 k_scan_agg_range2(AggParams P, RangeAux R, RangeOut O) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -770,7 +793,8 @@ k_scan_agg_range2(AggParams P, RangeAux R, RangeOut O) {
             const uint32_t erow = (uint32_t)pk1;
             while ((pos < epos || (pos == epos && row < erow)) &&
                    !__any(lost)) {
-                const RgDesc rg = P.rgs[R.sst_rgs[loff + (int32_t)pos]];
+                const int32_t rgi = R.sst_rgs[loff + (int32_t)pos];
+                const RgDesc rg = P.rgs[rgi];
                 const uint64_t* S =
                     (const uint64_t*)hx_ptr(P.blob, P.dec, rg.series_off);
                 const int64_t* T =
@@ -870,6 +894,13 @@ k_scan_agg_range2(AggParams P, RangeAux R, RangeOut O) {
                         a1 = !dup;
                     }
                     my_matched += (a0 ? 1u : 0u) + (a1 ? 1u : 0u);
+                    // null values: matched above, no update — each row of
+                    // the pair on its own, so the merge below sees only
+                    // rows that carry a value
+                    if (NULLS) {
+                        if (a0) a0 = row_valid(P, (uint32_t)rgi, r0);
+                        if (a1) a1 = row_valid(P, (uint32_t)rgi, r1);
+                    }
                     // in-lane pair merge, then direct LDS updates
                     const bool merge = a0 && a1 && (s0 == s1);
                     if (merge) {
@@ -1112,6 +1143,8 @@ struct ScanRowsParams {
     int32_t _pad;
     unsigned long long* cursor;
     unsigned long long cap;
+    uint64_t* out_valid;      // 1 / 0 per survivor: value present (nullable;
+                              // set when the plan staged a validity bitmap)
 };
 
 extern "C" __global__ void __launch_bounds__(256)
@@ -1148,6 +1181,8 @@ k_scan_rows(ScanRowsParams R) {
                     R.out_series[j] = s;
                     R.out_ts[j] = t;
                     R.out_value[j] = V[r];
+                    if (R.out_valid)
+                        R.out_valid[j] = row_valid(P, rgi, r) ? 1ull : 0ull;
                     if (R.out_seq) {
                         uint64_t q = row_seq(P, sst, rg, r);
                         R.out_seq[j] = R.seq_rowidx
@@ -1553,6 +1588,127 @@ k_copy_u64(const uint8_t* blob, const uint8_t* dec_in, uint8_t* dec,
         uint64_t* dst = (uint64_t*)(dec + (c.dst_off & OFF_MASK));
         for (uint32_t i = threadIdx.x; i < c.n_values; i += blockDim.x)
             dst[i] = src[i];
+    }
+}
+
+// ---------------------------------------------------------------------------
+// OPTIONAL-column PLAIN pages (DESIGN §4 kernel 1c). Two things keep such a
+// page from being read in place. A v1 page that went through the Snappy
+// decoder sits in dec as {level block, values}; the block is 6-8 bytes for a
+// page without nulls, so the values start at a byte offset that is not a
+// multiple of 8. And a page with nulls stores only its n_valid present
+// values, packed. One workgroup per page writes the dense, 64-byte-aligned
+// n_rows column the scan kernels index by row:
+//   * no bitmap: rank(r) = r, a realigning copy;
+//   * bitmap: tiles of 8192 rows = 128 words; popcount per word, exclusive
+//     scan over the tile in LDS, rank carried from tile to tile; a valid row
+//     gathers packed[rank], a null row stores 0.
+// A packed value is read as the two ALIGNED words that straddle it,
+// funnel-shifted together (no unaligned 8-byte load); the value whose upper
+// word would reach past the page is assembled from bytes, so nothing outside
+// [src, src + src_len) is read, and a rank at or above n_valid is never
+// followed. Stores are 8 B per lane, coalesced. A descriptor that does not
+// fit its source, is not 8-byte aligned, or whose bitmap disagrees with
+// n_valid counts one decode error (the exec then fails with HX_ERR_FORMAT);
+// in the first two cases nothing is written.
+// ---------------------------------------------------------------------------
+#define EXPAND_TILE_WORDS 128u   // 8192 rows
+
+__device__ __forceinline__ uint64_t packed_u64(const uint8_t* body,
+                                               uint32_t mis, uint64_t w_base,
+                                               uint32_t src_len, uint32_t k) {
+    const uint64_t* w = (const uint64_t*)(body - mis);
+    if (mis == 0) return w[k];
+    if (w_base + 8ull * (k + 2) <= src_len)
+        return (w[k] >> (mis * 8u)) | (w[k + 1] << (64u - mis * 8u));
+    uint64_t v = 0;
+    for (int b = 0; b < 8; b++)
+        v |= (uint64_t)body[8ull * k + b] << (8 * b);
+    return v;
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+k_expand_optional(const uint8_t* blob, const uint8_t* dec_in, uint8_t* dec,
+                  const ExpandPageDesc* __restrict__ pages, uint32_t n_pages,
+                  unsigned long long* err_flag) {
+    __shared__ uint32_t wrank[EXPAND_TILE_WORDS];   // exclusive, within tile
+    __shared__ uint32_t tile_total;
+    for (uint32_t pg = blockIdx.x; pg < n_pages; pg += gridDim.x) {
+        const ExpandPageDesc pd = pages[pg];
+        if ((uint64_t)pd.lvl_bytes + (uint64_t)pd.n_valid * 8 > pd.src_len ||
+            ((pd.src_off | pd.dst_off | pd.bitmap_off) & 7u) ||
+            pd.n_valid > pd.n_rows ||
+            (!pd.bitmap_off && pd.n_valid != pd.n_rows)) {
+            if (threadIdx.x == 0) atomicAdd(err_flag, 1ull);
+            continue;
+        }
+        const uint8_t* body = hx_ptr(blob, dec_in, pd.src_off) + pd.lvl_bytes;
+        uint64_t* dst = (uint64_t*)(dec + (pd.dst_off & OFF_MASK));
+        // src_off is 8-aligned, so the misalignment is lvl_bytes & 7 and the
+        // aligned-down start lies inside the page
+        const uint32_t mis = pd.lvl_bytes & 7u;
+        const uint64_t w_base = pd.lvl_bytes - mis;  // byte offset of word 0
+        if (!pd.bitmap_off) {
+            for (uint32_t i = threadIdx.x; i < pd.n_rows; i += blockDim.x)
+                dst[i] = packed_u64(body, mis, w_base, pd.src_len, i);
+            continue;
+        }
+        const uint64_t* bm = (const uint64_t*)(blob + pd.bitmap_off);
+        const uint32_t n_words = (pd.n_rows + 63u) >> 6;
+        uint32_t carry = 0;       // valid rows before this tile
+        bool bad = false;
+        for (uint32_t w0 = 0; w0 < n_words; w0 += EXPAND_TILE_WORDS) {
+            const uint32_t tw = n_words - w0 < EXPAND_TILE_WORDS
+                                    ? n_words - w0 : EXPAND_TILE_WORDS;
+            __syncthreads();   // previous tile's wrank fully consumed
+            if (threadIdx.x < EXPAND_TILE_WORDS) {
+                uint64_t wv = threadIdx.x < tw ? bm[w0 + threadIdx.x] : 0ull;
+                // bits at and above n_rows do not count
+                const uint32_t row0 = (w0 + threadIdx.x) << 6;
+                if (threadIdx.x < tw && pd.n_rows - row0 < 64u)
+                    wv &= (1ull << (pd.n_rows - row0)) - 1ull;
+                wrank[threadIdx.x] = (uint32_t)__popcll(wv);
+            }
+            __syncthreads();
+            // inclusive Hillis-Steele scan over the 128 counts
+            for (uint32_t d = 1; d < EXPAND_TILE_WORDS; d <<= 1) {
+                uint32_t add = 0;
+                if (threadIdx.x < EXPAND_TILE_WORDS && threadIdx.x >= d)
+                    add = wrank[threadIdx.x - d];
+                __syncthreads();
+                if (threadIdx.x < EXPAND_TILE_WORDS) wrank[threadIdx.x] += add;
+                __syncthreads();
+            }
+            if (threadIdx.x == 0) tile_total = wrank[EXPAND_TILE_WORDS - 1];
+            __syncthreads();
+            const uint32_t r_end = (w0 + tw) << 6 < pd.n_rows
+                                       ? (w0 + tw) << 6 : pd.n_rows;
+            for (uint32_t r = (w0 << 6) + threadIdx.x; r < r_end;
+                 r += blockDim.x) {
+                const uint32_t wi = (r >> 6) - w0;
+                const uint64_t wv = bm[w0 + wi];
+                uint64_t v = 0;
+                if ((wv >> (r & 63u)) & 1ull) {
+                    const uint32_t before =
+                        (uint32_t)__popcll(wv & ((1ull << (r & 63u)) - 1ull));
+                    // exclusive rank of the word = inclusive - its own count
+                    const uint32_t own = (uint32_t)__popcll(
+                        (r | 63u) < pd.n_rows
+                            ? wv
+                            : wv & ((1ull << (pd.n_rows & 63u)) - 1ull));
+                    const uint32_t k = carry + wrank[wi] - own + before;
+                    if (k < pd.n_valid)
+                        v = packed_u64(body, mis, w_base, pd.src_len, k);
+                    else
+                        bad = true;
+                }
+                dst[r] = v;
+            }
+            carry += tile_total;
+        }
+        // the bitmap must account for exactly the packed values
+        if (threadIdx.x == 0 && carry != pd.n_valid) bad = true;
+        if (bad) atomicAdd(err_flag, 1ull);
     }
 }
 
@@ -2523,6 +2679,16 @@ hipError_t launch_snappy(hipStream_t s, const uint8_t* blob, uint8_t* dec,
     return hipGetLastError();
 }
 
+hipError_t launch_expand_optional(hipStream_t s, const uint8_t* blob,
+                                  uint8_t* dec, const ExpandPageDesc* pages,
+                                  uint32_t n_pages,
+                                  unsigned long long* err_flag) {
+    uint32_t grid = n_pages > 65535 ? 65535 : n_pages;
+    hipLaunchKernelGGL(k_expand_optional, dim3(grid), dim3(256), 0, s,
+                       blob, dec, dec, pages, n_pages, err_flag);
+    return hipGetLastError();
+}
+
 hipError_t launch_copy_u64(hipStream_t s, const uint8_t* blob, uint8_t* dec,
                            const CopyDesc* descs, uint32_t n_descs) {
     uint32_t grid = n_descs > 4096 ? 4096 : n_descs;
@@ -2531,9 +2697,15 @@ hipError_t launch_copy_u64(hipStream_t s, const uint8_t* blob, uint8_t* dec,
     return hipGetLastError();
 }
 
-hipError_t launch_scan_agg(hipStream_t s, const AggParams& p, uint32_t grid) {
+hipError_t launch_scan_agg(hipStream_t s, const AggParams& p, uint32_t grid,
+                           bool nulls) {
     if (grid == 0) grid = p.n_rgs > 65535 ? 65535 : (p.n_rgs ? p.n_rgs : 1);
-    hipLaunchKernelGGL(k_scan_agg, dim3(grid), dim3(256), 0, s, p);
+    // NULLS is a launch-level template parameter, as for the range kernel:
+    // a wrapper around one shared body costs the null-off instance 3 VGPRs
+    if (nulls)
+        hipLaunchKernelGGL(k_scan_agg<true>, dim3(grid), dim3(256), 0, s, p);
+    else
+        hipLaunchKernelGGL(k_scan_agg<false>, dim3(grid), dim3(256), 0, s, p);
     return hipGetLastError();
 }
 
@@ -2559,30 +2731,33 @@ hipError_t launch_range_bounds(hipStream_t s, const AggParams& p,
     return hipGetLastError();
 }
 
-template <bool MM>
+template <bool MM, bool NULLS>
 static hipError_t launch_range2_inst(hipStream_t s, const AggParams& p,
                                      const RangeAux& r, const RangeOut& o) {
     // per slot: key 8 + sum 8 + cnt 4 [+ min 8 + max 8] + sort index 2
     const size_t lds = (size_t)r.ne * (MM ? 38 : 22);
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(
-            reinterpret_cast<const void*>(&k_scan_agg_range2<MM>),
+            reinterpret_cast<const void*>(&k_scan_agg_range2<MM, NULLS>),
             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(k_scan_agg_range2<MM>, dim3(r.n_blocks), dim3(256),
-                       lds, s, p, r, o);
+    hipLaunchKernelGGL((k_scan_agg_range2<MM, NULLS>), dim3(r.n_blocks),
+                       dim3(256), lds, s, p, r, o);
     return hipGetLastError();
 }
 
 hipError_t launch_scan_agg_range2(hipStream_t s, const AggParams& p,
                                   const RangeAux& r, bool minmax,
-                                  const RangeOut& out) {
+                                  bool nulls, const RangeOut& out) {
     // the sort permutation is u16 and the slot mask needs a power of two
     if (r.ne == 0 || (r.ne & (r.ne - 1)) || r.ne > 32768u)
         return hipErrorInvalidValue;
-    return minmax ? launch_range2_inst<true>(s, p, r, out)
-                  : launch_range2_inst<false>(s, p, r, out);
+    if (nulls)
+        return minmax ? launch_range2_inst<true, true>(s, p, r, out)
+                      : launch_range2_inst<false, true>(s, p, r, out);
+    return minmax ? launch_range2_inst<true, false>(s, p, r, out)
+                  : launch_range2_inst<false, false>(s, p, r, out);
 }
 
 hipError_t launch_place_runs(hipStream_t s, const RangePlace& q) {
@@ -2600,7 +2775,7 @@ hipError_t launch_scan_rows(hipStream_t s, const AggParams& p,
                             uint64_t* out_series, long long* out_ts,
                             double* out_value, unsigned long long* cursor,
                             unsigned long long cap, uint64_t* out_seq,
-                            int32_t seq_rowidx) {
+                            int32_t seq_rowidx, uint64_t* out_valid) {
     ScanRowsParams R;
     R.P = p;
     R.rg_first = rg_first;
@@ -2613,6 +2788,7 @@ hipError_t launch_scan_rows(hipStream_t s, const AggParams& p,
     R._pad = 0;
     R.cursor = cursor;
     R.cap = cap;
+    R.out_valid = out_valid;
     uint32_t n = rg_last - rg_first;
     hipLaunchKernelGGL(k_scan_rows, dim3(n > 4096 ? 4096 : (n ? n : 1)),
                        dim3(256), 0, s, R);

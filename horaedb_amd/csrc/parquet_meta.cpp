@@ -235,27 +235,26 @@ std::vector<PageDesc> walk_pages(const uint8_t* buf, size_t len,
         pd.uncompressed_size = uncomp;
         if (pd.page_type == 0 && optional_col) {
             // v1 data page of an OPTIONAL column: definition levels are a
-            // 4-byte-length-prefixed RLE block at the START of the payload
-            // (inside the compressed stream when the page is compressed —
-            // that case is not staged here). The metric schema's rows have
-            // no nulls in practice (arrow-rs writes def levels for nullable
-            // columns anyway); reject real nulls loudly.
-            if (pd.null_count > 0)
-                throw std::runtime_error(
-                    "v1 data page has nulls (null_count > 0): nullable "
-                    "values are outside the metric scan contract");
-            if (codec != CODEC_UNCOMPRESSED)
-                throw std::runtime_error(
-                    "v1 OPTIONAL column with compressed pages: def levels "
-                    "are inside the compressed stream (unsupported; write "
-                    "REQUIRED columns or uncompressed pages)");
+            // 4-byte-length-prefixed RLE block at the START of the page
+            // body. When the page is compressed the block is inside the
+            // compressed stream: the caller finds it after (or, for Snappy,
+            // by a prefix of) the codec step. Whether the levels hold nulls
+            // is the caller's business too — it decodes them (def_levels.h)
+            // rather than trust the optional statistics.
+            if (codec != CODEC_UNCOMPRESSED) {
+                pd.levels_in_stream = 1;
+                pos += hdr_len + size_t(comp);
+                seen += pd.num_values;
+                pages.push_back(pd);
+                continue;
+            }
             if (size_t(comp) < 4)
                 throw std::runtime_error("v1 def-level prefix truncated");
             const uint8_t* pl = buf + pos + hdr_len;
             uint32_t rle_len = (uint32_t)pl[0] | ((uint32_t)pl[1] << 8) |
                                ((uint32_t)pl[2] << 16) |
                                ((uint32_t)pl[3] << 24);
-            if (4 + (int64_t)rle_len >= comp)
+            if (4 + (int64_t)rle_len > comp)
                 throw std::runtime_error("v1 def-level block exceeds page");
             pd.def_level_bytes = int32_t(4 + rle_len);
         }

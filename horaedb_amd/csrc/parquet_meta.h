@@ -73,12 +73,17 @@ struct PageDesc {
                               // uncompressed: 4-byte-prefixed RLE block)
     int32_t is_compressed = 1; // data page v2 is_compressed flag (v1: always)
     int64_t null_count = -1;  // v1 statistics null_count (-1 = absent)
+    int32_t levels_in_stream = 0;  // v1 OPTIONAL compressed page: the level
+                              // block opens the DEcompressed body, so
+                              // def_level_bytes is 0 here
 };
 
 // Walk page headers of a column chunk (buf = the chunk's bytes; base_off =
 // its absolute file offset). Stops after `num_values` data values seen.
 // optional_col + codec let v1 pages of OPTIONAL columns account for their
-// embedded definition-level block (nulls themselves are rejected).
+// embedded definition-level block: sized here when the page is uncompressed,
+// flagged levels_in_stream when it is inside the compressed stream. The
+// levels are not decoded here; callers decide what nulls mean.
 std::vector<PageDesc> walk_pages(const uint8_t* buf, size_t len,
                                  int64_t base_off, int64_t num_values,
                                  bool optional_col = false,

@@ -64,7 +64,8 @@ class _ResultTable(C.Structure):
 class _ColBatch(C.Structure):
     _fields_ = [("n_rows", C.c_size_t), ("n_cols", C.c_size_t),
                 ("cols", C.POINTER(C.c_void_p)),
-                ("col_types", C.POINTER(C.c_int32))]
+                ("col_types", C.POINTER(C.c_int32)),
+                ("validity", C.POINTER(C.POINTER(C.c_uint8)))]
 
 
 class _ExecStats(C.Structure):
@@ -120,6 +121,9 @@ def _load():
                                      C.POINTER(C.c_uint64), C.POINTER(C.c_int64),
                                      C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                      C.POINTER(C.c_int64)]
+    lib.hx_debug_page_levels.argtypes = [
+        C.c_char_p, C.c_int32, C.c_char_p, C.POINTER(C.c_uint64), C.c_uint64,
+        C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     return lib
 
 
@@ -469,6 +473,7 @@ class Store:
             keep.append(parr)
         ds = self._devset(devices, keep)
         chunks = []
+        valid_parts = []   # per batch: the f64 value column's validity
 
         _BATCH = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.POINTER(_ColBatch))
 
@@ -495,6 +500,13 @@ class Store:
                 ptr = C.cast(b.cols[i], C.POINTER(C.c_uint64))
                 arr = np.ctypeslib.as_array(ptr, shape=(b.n_rows,)).copy()
                 cols.append(arr.view(dt))
+                if t == 2 and b.validity and b.validity[i]:
+                    bits = np.ctypeslib.as_array(
+                        b.validity[i], shape=((b.n_rows + 7) // 8,))
+                    valid_parts.append(np.unpackbits(
+                        bits, bitorder="little")[:b.n_rows].astype(bool))
+                elif t == 2:
+                    valid_parts.append(np.ones(b.n_rows, dtype=bool))
             chunks.append(cols)
             if batch_limit is not None and len(chunks) >= batch_limit:
                 return 1
@@ -519,6 +531,10 @@ class Store:
             parts = [c[i] for c in chunks]
             out[names[sel[i]]] = (np.concatenate(parts) if parts else
                                   np.empty(0))
+        # only when the value column carried a bitmap (the store holds null
+        # values); values at rows where it is False are unspecified
+        if valid_parts and not all(v.all() for v in valid_parts):
+            out["value_valid"] = np.concatenate(valid_parts)
         return out
 
 
@@ -533,3 +549,17 @@ def write_sst_native(path, series, ts, value, seq, row_group=8192):
         path.encode(), series.ctypes.data_as(C.POINTER(C.c_uint64)),
         ts.ctypes.data_as(C.POINTER(C.c_int64)),
         value.ctypes.data_as(C.POINTER(C.c_double)), seq, n, row_group))
+
+
+def page_levels(path, row_group, column, max_rows=1 << 20):
+    """Staging's view of one column chunk's definition levels (test hook
+    hx_debug_page_levels; no GPU needed): returns (valid, n_valid,
+    level_bytes) where valid is a bool array of the chunk's rows."""
+    words = np.zeros((max_rows + 63) // 64, dtype=np.uint64)
+    n_rows, n_valid, lvl = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+    _check(_lib.hx_debug_page_levels(
+        path.encode(), row_group, column.encode(),
+        words.ctypes.data_as(C.POINTER(C.c_uint64)), len(words),
+        C.byref(n_rows), C.byref(n_valid), C.byref(lvl)))
+    bits = np.unpackbits(words.view(np.uint8), bitorder="little")
+    return bits[:n_rows.value].astype(bool), n_valid.value, lvl.value

@@ -34,7 +34,10 @@ enum {
     HX_OK             = 0,
     HX_ERR_IO         = 1,   /* file missing/unreadable */
     HX_ERR_FORMAT     = 2,   /* not a parquet SST / unsupported layout */
-    HX_ERR_UNSUPPORTED= 3,   /* encoding/codec outside round-1 scope */
+    HX_ERR_UNSUPPORTED= 3,   /* encoding/codec outside round-1 scope; nulls
+                                in series_id/timestamp/__seq__, in a
+                                dictionary-encoded or Binary value column,
+                                under Append mode, or in compaction inputs */
     HX_ERR_NO_GPU     = 4,   /* HIP runtime/device unavailable */
     HX_ERR_HIP        = 5,   /* HIP call failed (see hx_last_error) */
     HX_ERR_INVALID    = 6,   /* bad argument */
@@ -91,6 +94,13 @@ enum {
     HX_AGG_MAX   = 1u << 3,
     HX_AGG_AVG   = 1u << 4,   /* finalized as sum/count */
 };
+/* Null values (OPTIONAL f64 value column): a row with a null value is still
+ * a row — it passes or fails the filter and takes part in dedup like any
+ * other (a newer null shadows an older value of the same PK, and is shadowed
+ * by a newer value) and counts in hx_exec_stats.rows_matched. The aggregates
+ * run over the non-null survivors: sum/min/max/avg ignore nulls and count
+ * counts values. A group all of whose surviving values are null is not
+ * emitted (the result table has no validity channel). */
 typedef struct {
     uint32_t ops;         /* OR of HX_AGG_*  (over the value column) */
     int64_t  bucket_ms;   /* 0: group by series_id; >0: by (series_id,
@@ -136,6 +146,13 @@ typedef struct {
     const void* const* cols;      /* col i: n_rows × 8B elements, or ONE
                                      hx_bytes_col when col_types[i] == 3    */
     const int32_t*     col_types; /* 0=u64, 1=i64(ts ms), 2=f64, 3=bytes    */
+    /* Appended member (batches are passed by pointer, so callers built
+     * against the four-member struct keep working). NULL: every value of
+     * every column is present. Otherwise one pointer per column: NULL (all
+     * rows valid) or an LSB-first bitmap of n_rows bits, 1 = value present.
+     * Only an f64 value column can carry nulls; the 8 bytes in cols[i] at a
+     * null row are unspecified. */
+    const uint8_t* const* validity;
 } hx_col_batch;
 typedef int32_t (*hx_batch_cb)(void* ctx, const hx_col_batch* batch); /* nonzero => stop */
 
