@@ -2,7 +2,11 @@
 // ObjectBasedStorage::try_new + Manifest::find_ssts), staging (replaces the
 // ParquetExec reader factory, read.rs:78-93, incl. the reference's row-group
 // pruning pushdown read.rs:459-470), and the GPU execution path (DESIGN.md
-// §3-§5). Compute is GPU-only; no CPU fallback exists here.
+// §3-§5). Compute is GPU-only; no CPU fallback exists here. Of staging, this
+// file keeps the slot layout, the reader threads and the upload; what happens
+// to one column chunk between its bytes and its descriptors (page walk, host
+// codec step, definition levels, Zstd via dlopen) is stage_chunk.{h,cpp},
+// which needs no GPU to build or run.
 #include "../../include/horaedb_hx.h"
 #include "parquet_meta.h"
 #include "parquet_writer.h"
@@ -28,40 +32,11 @@
 
 #include "hx_kernels.h"
 #include "hx_internal.h"
-#include "snappy_stored.h"
+#include "stage_chunk.h"
 #include "def_levels.h"
 
-// ---------------------------------------------------------------------------
-// Zstd page codec (config.rs:84 includes Zstd): decompressed on the HOST at
-// staging time into the page blob — the same place SURVEY §7 allows for
-// inherently serial codecs — so the kernels see raw PLAIN pages. The image
-// ships libzstd.so.1 without a dev header; dlopen with self-declared
-// prototypes (stable ZSTD_* ABI). Fails loudly when the library is absent.
-// ---------------------------------------------------------------------------
-#include <dlfcn.h>
-
-namespace {
-typedef size_t (*zstd_decompress_fn)(void*, size_t, const void*, size_t);
-typedef unsigned (*zstd_iserror_fn)(size_t);
-
-struct ZstdLib {
-    zstd_decompress_fn decompress = nullptr;
-    zstd_iserror_fn is_error = nullptr;
-    bool ok = false;
-    ZstdLib() {
-        void* h = dlopen("libzstd.so.1", RTLD_NOW | RTLD_LOCAL);
-        if (!h) return;
-        decompress = (zstd_decompress_fn)dlsym(h, "ZSTD_decompress");
-        is_error = (zstd_iserror_fn)dlsym(h, "ZSTD_isError");
-        ok = decompress && is_error;
-    }
-};
-
-const ZstdLib& zstd() {
-    static ZstdLib z;
-    return z;
-}
-}  // namespace
+using hx::align64;
+using hx::ChunkRef;
 
 // ---------------------------------------------------------------------------
 // error plumbing
@@ -87,15 +62,6 @@ static hx_status fail(hx_status code, const std::string& msg) {
 // catalog (hx_open)
 // ---------------------------------------------------------------------------
 namespace {
-
-struct ChunkRef {
-    int32_t codec = 0;
-    bool required = true;
-    int64_t chunk_start = 0;
-    int64_t comp_size = 0;
-    int64_t uncomp_size = 0;
-    int64_t num_values = 0;
-};
 
 struct CatRg {
     int64_t n_rows = 0;
@@ -473,115 +439,49 @@ static int hip_device_count() {
     return n;
 }
 
-static size_t align64(size_t x) { return (x + 63) & ~size_t(63); }
+namespace {
 
-// Definition levels of one data page of an OPTIONAL column, read from the
-// place that holds them: a v2 page keeps them outside the
-// compressed region (page[0, def_level_bytes)); an uncompressed v1 page opens
-// with the length-prefixed block (walk_pages sized it); a compressed v1 page
-// has the block inside the stream — a Snappy stream gives it up through a
-// prefix decode, a Zstd page after the host decompress (`post`, the whole
-// decompressed body; unused otherwise). `page` is the page's bytes as stored.
-// *in_stream receives the block's size inside the decompressed body (0 when
-// def_level_bytes already accounts for it). bitmap may be null. Returns an
-// empty string, or what is wrong with the page.
-static std::string page_levels(const hx::PageDesc& dp, int32_t codec,
-                               const uint8_t* page, const uint8_t* post,
-                               size_t post_len, uint64_t* bitmap,
-                               uint32_t* in_stream, uint32_t* n_valid) {
-    *in_stream = 0;
-    const uint8_t* lv = nullptr;
-    size_t lv_len = 0;
-    std::vector<uint8_t> pre;
-    if (!dp.levels_in_stream) {
-        const size_t skip = dp.page_type == 0 ? 4 : 0;  // v1 length prefix
-        if (size_t(dp.def_level_bytes) < skip) return "level block truncated";
-        lv = page + skip;
-        lv_len = size_t(dp.def_level_bytes) - skip;
-    } else if (codec == hx::CODEC_SNAPPY) {
-        uint8_t head[4];
-        if (hx_snappy_prefix(page, size_t(dp.compressed_size), head, 4) != 4)
-            return "Snappy page too short for its level block";
-        // framing against the declared page size; the prefix decode below
-        // fails if the stream is shorter than that
-        const uint64_t rle = uint64_t(head[0]) | uint64_t(head[1]) << 8 |
-                             uint64_t(head[2]) << 16 | uint64_t(head[3]) << 24;
-        if (4 + rle > uint64_t(dp.uncompressed_size))
-            return "v1 def-level block exceeds page";
-        const uint32_t bb = uint32_t(4 + rle);
-        pre.resize(bb);
-        if (hx_snappy_prefix(page, size_t(dp.compressed_size), pre.data(),
-                             bb) != long(bb))
-            return "Snappy stream ends inside the level block";
-        lv = pre.data() + 4;
-        lv_len = bb - 4;
-        *in_stream = bb;
-    } else {
-        uint32_t bb = 0;
-        if (!post || hx_level_block_bytes(post, post_len, &bb) != HX_LVL_OK)
-            return "v1 def-level block exceeds page";
-        lv = post + 4;
-        lv_len = bb - 4;
-        *in_stream = bb;
-    }
-    if (dp.num_values < 0) return "negative value count";
-    const int rc = hx_levels_to_bitmap(lv, lv_len, uint32_t(dp.num_values),
-                                       bitmap, n_valid);
-    if (rc != HX_LVL_OK)
-        return "malformed definition levels (code " + std::to_string(rc) + ")";
-    return std::string();
-}
+struct PageJob {  // one (rg, col) column chunk to read + stage
+    StagedSst* ss;
+    const ChunkRef* cr;
+    hx::ChunkRole role;
+    size_t dst_off;      // blob offset of its slot, hx::chunk_reserve bytes
+    size_t bitmap_off;   // blob offset of its validity words, 0 = none
+};
 
-static hx_status stage_device(hx_prepared* P, DevPlan& plan,
-                              std::vector<StagedSst*>& members) {
+}  // namespace
+
+// Layout pass: SstDev / RgDesc entries in plan order, the dense dec arrays
+// of each SST, and one job with a blob slot per staged column chunk (3 per
+// row group, 4 where per-row seqs are staged). Returns the dec bytes laid out
+// so far; the decode targets are reserved behind them during the page walk
+// (which chunks need one is not known until their headers are read).
+static size_t layout_jobs(hx_prepared* P, DevPlan& plan,
+                          std::vector<StagedSst*>& members,
+                          std::vector<PageJob>& jobs) {
     const bool bytes_val = P->h->bytes_value;
-    // ---- layout pass ----------------------------------------------------
-    struct PageJob {  // one (rg, col) data page to read+pack
-        StagedSst* ss;
-        int rg_cat;         // catalog rg index
-        int col;            // 0 series 1 ts 2 value
-        int64_t chunk_start, comp_size, uncomp_size, num_values;
-        int64_t row_base;
-        int32_t codec;
-        bool required;
-        size_t dst_off;     // blob offset reserved (chunk_size upper bound)
-        size_t bitmap_off = 0;  // OPTIONAL value column: blob offset reserved
-                                // for the page's validity words (64-aligned)
-        bool has_nulls = false; // filled after page walk: the words are live
-        // filled after page walk:
-        uint64_t final_off = 0;  // RgDesc offset value (blob or OFF_DEC)
-    };
-
-    std::vector<PageJob> jobs;
     size_t blob_off = 0, dec_off = 0;
-
+    auto dense = [&](int64_t rows) {
+        const uint64_t off = dec_off;
+        dec_off = align64(dec_off + size_t(rows) * 8);
+        return off;
+    };
     for (StagedSst* ss : members) {
         hx::SstDev sd{};
         sd.cluster = ss->cluster;
         sd.rank = ss->rank;
-        sd.dense_series = 0;
-        sd.dense_ts = 0;
         sd.seq = ss->cat->seq;
-        sd.dense_seq = 0;
         sd.n_staged = ss->staged_rows;
-        bool need_dense = ss->cluster >= 0;
+        const bool need_dense = ss->cluster >= 0;
         // per-row seqs are only consulted by the cross-SST dedup, so they
         // are staged only for overlap-cluster members with mixed seqs
-        bool need_seq = need_dense && ss->cat->seq_mixed;
+        const bool need_seq = need_dense && ss->cat->seq_mixed;
         if (need_dense) {
-            sd.dense_series = hx::OFF_DEC | dec_off;
-            dec_off = align64(dec_off + size_t(ss->staged_rows) * 8);
-            sd.dense_ts = hx::OFF_DEC | dec_off;
-            dec_off = align64(dec_off + size_t(ss->staged_rows) * 8);
+            sd.dense_series = hx::OFF_DEC | dense(ss->staged_rows);
+            sd.dense_ts = hx::OFF_DEC | dense(ss->staged_rows);
         }
-        if (need_seq) {
-            sd.dense_seq = hx::OFF_DEC | dec_off;
-            dec_off = align64(dec_off + size_t(ss->staged_rows) * 8);
-        }
-        if (P->h->bytes_value) {
-            ss->bytes_handles = dec_off;
-            dec_off = align64(dec_off + size_t(ss->staged_rows) * 8);
-        }
+        if (need_seq) sd.dense_seq = hx::OFF_DEC | dense(ss->staged_rows);
+        if (bytes_val) ss->bytes_handles = dense(ss->staged_rows);
         ss->dev_slot = (int)plan.ssts.size();
         plan.ssts.push_back(sd);
 
@@ -598,35 +498,20 @@ static hx_status stage_device(hx_prepared* P, DevPlan& plan,
             if (prev_rg_desc >= 0) plan.rgs[prev_rg_desc].next_rg = this_desc;
             prev_rg_desc = this_desc;
             plan.rgs.push_back(rd);
-            const int n_stage_cols = need_seq ? 4 : 3;
-            for (int c = 0; c < n_stage_cols; c++) {
-                const ChunkRef& cr = rg.cols[c];
-                PageJob j;
+            for (int c = 0; c < (need_seq ? 4 : 3); c++) {
+                PageJob j{};
                 j.ss = ss;
-                j.rg_cat = rgi;
-                j.col = c;
-                j.chunk_start = cr.chunk_start;
-                j.comp_size = cr.comp_size;
-                j.uncomp_size = cr.uncomp_size;
-                j.num_values = cr.num_values;
-                j.codec = cr.codec;
-                j.required = cr.required;
-                j.row_base = row_base;
+                j.cr = &rg.cols[c];
+                j.role.col = c;
+                j.role.bytes_value = bytes_val;
+                j.role.update_mode = P->h->update_mode;
+                j.role.row_base = row_base;
+                j.role.bytes_handles = ss->bytes_handles;
                 j.dst_off = blob_off;
-                // Zstd chunks are decompressed in place at staging: reserve
-                // the larger of the on-disk and decompressed sizes
-                size_t reserve = size_t(cr.comp_size);
-                if (cr.codec == hx::CODEC_ZSTD)
-                    reserve = std::max(reserve, size_t(cr.uncomp_size));
-                // Snappy chunks: room to shift a stored-literal page so its
-                // body lands 64-byte aligned (pad <= 63, see the page walk)
-                if (cr.codec == hx::CODEC_SNAPPY) reserve += 64;
-                blob_off = align64(blob_off + reserve);
-                if (c == 2 && !cr.required && !bytes_val &&
-                    cr.num_values > 0) {
+                blob_off = align64(blob_off + hx::chunk_reserve(*j.cr));
+                if (const size_t bm = hx::bitmap_reserve(*j.cr, c, bytes_val)) {
                     j.bitmap_off = blob_off;
-                    blob_off = align64(blob_off +
-                                       (size_t(cr.num_values) + 63) / 64 * 8);
+                    blob_off = align64(blob_off + bm);
                 }
                 jobs.push_back(j);
             }
@@ -634,549 +519,111 @@ static hx_status stage_device(hx_prepared* P, DevPlan& plan,
             plan.rows_scanned += rg.n_rows;
         }
     }
-    // dec region for non-overlap delta pages is appended after the page walk
-    // (we do not know which chunks are delta until headers are read); reserve
-    // lazily via an atomic cursor.
     plan.blob_bytes = blob_off;
+    return dec_off;
+}
 
-    // ---- read + page walk (parallel over jobs) --------------------------
-    if (plan.h_blob == nullptr && blob_off > 0) {
-        if (hipHostMalloc((void**)&plan.h_blob, blob_off,
-                          hipHostMallocDefault) == hipSuccess) {
-            plan.h_blob_pinned = true;
-        } else {
-            plan.h_blob = (uint8_t*)malloc(blob_off);
-            plan.h_blob_pinned = false;
-            if (!plan.h_blob) return fail(HX_ERR_IO, "staging alloc failed");
-        }
-    }
-
+// Read + page walk, parallel over jobs: each worker claims a job, reads the
+// chunk and stages it into the job's slot (stage_chunk.h). Workers share the
+// dec cursor (atomic) and the error string; each collects descriptors in a
+// bundle of its own, and the plan takes the bundles one after the other once
+// all have joined. Descriptor order therefore depends on thread timing, as it
+// always has: every decode kernel takes one descriptor per wave or workgroup
+// and none looks at its neighbours, so the order carries no meaning.
+static hx_status stage_chunks(DevPlan& plan, const std::vector<PageJob>& jobs,
+                              std::vector<hx::ChunkResult>& results,
+                              std::atomic<size_t>& dec) {
+    const unsigned n_threads = std::min<unsigned>(
+        16, std::max(1u, std::thread::hardware_concurrency()));
+    std::vector<hx::StagedPages> bundles(n_threads);
     std::atomic<size_t> next{0};
     std::atomic<int> err_flag{0};
-    std::mutex mu;  // guards delta/copy/dec_off bookkeeping + error string
+    std::mutex mu;  // guards the error string, nothing else
     std::string err_msg;
-    // per-rg descriptor index: jobs are 3 per rg in plan order
-    auto worker = [&]() {
+    auto worker = [&](hx::StagedPages& out) {
         std::vector<uint8_t> tmp;
-        int last_fd = -1;
-        const CatSst* last_cat = nullptr;
+        int fd = -1;
+        const CatSst* cat = nullptr;
         for (;;) {
-            size_t i = next.fetch_add(1);
+            const size_t i = next.fetch_add(1);
             if (i >= jobs.size() || err_flag.load()) break;
-            PageJob& j = jobs[i];
-            if (last_cat != j.ss->cat) {
-                if (last_fd >= 0) close(last_fd);
-                last_fd = open(j.ss->cat->path.c_str(), O_RDONLY);
-                last_cat = j.ss->cat;
+            const PageJob& j = jobs[i];
+            if (cat != j.ss->cat) {
+                if (fd >= 0) close(fd);
+                cat = j.ss->cat;
+                fd = open(cat->path.c_str(), O_RDONLY);
             }
-            if (last_fd < 0) {
-                std::lock_guard<std::mutex> g(mu);
-                err_msg = "open " + j.ss->cat->path;
-                err_flag = 1;
-                break;
+            hx::StageStatus s;
+            if (fd < 0)
+                s.msg = "open " + cat->path;
+            else
+                s = hx::read_chunk(fd, cat->path, *j.cr, tmp);
+            if (s.ok()) {
+                hx::ChunkSlot slot;
+                slot.base = plan.h_blob + j.dst_off;
+                slot.off = j.dst_off;
+                slot.cap = hx::chunk_reserve(*j.cr);
+                if (j.bitmap_off) {
+                    slot.bitmap = (uint64_t*)(plan.h_blob + j.bitmap_off);
+                    slot.bitmap_off = j.bitmap_off;
+                    slot.bitmap_cap = hx::bitmap_reserve(
+                        *j.cr, j.role.col, j.role.bytes_value);
+                }
+                s = hx::stage_chunk(tmp.data(), *j.cr, j.role, slot, dec, out,
+                                    results[i]);
+                if (!s.ok()) s.msg = cat->path + ": " + s.msg;
             }
-            if (j.comp_size <= 0 || j.comp_size > (int64_t)1 << 31) {
+            if (!s.ok()) {
                 std::lock_guard<std::mutex> g(mu);
-                err_msg = j.ss->cat->path + ": implausible chunk size";
-                err_flag = 1;
-                break;
-            }
-            tmp.resize(j.comp_size);
-            if (pread(last_fd, tmp.data(), j.comp_size, j.chunk_start) !=
-                (ssize_t)j.comp_size) {
-                std::lock_guard<std::mutex> g(mu);
-                err_msg = "chunk read " + j.ss->cat->path;
-                err_flag = 1;
-                break;
-            }
-            std::vector<hx::PageDesc> pages;
-            try {
-                pages = hx::walk_pages(tmp.data(), tmp.size(), j.chunk_start,
-                                       j.num_values, !j.required, j.codec);
-            } catch (const std::exception& e) {
-                std::lock_guard<std::mutex> g(mu);
-                err_msg = j.ss->cat->path + ": " + e.what();
-                err_flag = 1;
-                break;
-            }
-            // layout contract: exactly one v1/v2 data page per chunk, plus an
-            // optional dictionary page (RLE_DICTIONARY chunks)
-            const hx::PageDesc* dp = nullptr;
-            const hx::PageDesc* dictp = nullptr;
-            int n_data = 0;
-            for (const auto& p : pages) {
-                if (p.page_type == 0 || p.page_type == 3) {
-                    dp = &p;
-                    n_data++;
-                } else if (p.page_type == 2) {
-                    dictp = &p;
-                }
-            }
-            if (err_flag.load()) break;
-            if (n_data != 1 || !dp || dp->num_values != j.num_values) {
-                std::lock_guard<std::mutex> g(mu);
-                err_msg = j.ss->cat->path + ": expected one data page per chunk "
-                          "(row-group 8192 writer contract)";
-                err_flag = 1;
-                break;
-            }
-            if (j.codec != hx::CODEC_UNCOMPRESSED &&
-                j.codec != hx::CODEC_SNAPPY &&
-                j.codec != hx::CODEC_ZSTD) {
-                std::lock_guard<std::mutex> g(mu);
-                err_msg = j.ss->cat->path + ": codec unsupported "
-                          "(uncompressed, Snappy and Zstd)";
-                err_flag = 1;
-                break;
-            }
-            if (j.codec == hx::CODEC_ZSTD && !zstd().ok) {
-                std::lock_guard<std::mutex> g(mu);
-                err_msg = j.ss->cat->path + ": Zstd pages but libzstd.so.1 "
-                          "is not loadable";
-                err_flag = 1;
-                break;
-            }
-            // size sanity BEFORE any copy: a corrupt header claiming
-            // def_level_bytes > compressed_size would underflow `payload`
-            // (size_t) and read/write out of bounds (walk_pages validates
-            // too; this guards the invariants this copy depends on)
-            size_t in_chunk = size_t(dp->payload_off - j.chunk_start);
-            if (dp->def_level_bytes < 0 ||
-                dp->def_level_bytes > dp->compressed_size ||
-                dp->payload_off < j.chunk_start ||
-                in_chunk + size_t(dp->compressed_size) > size_t(j.comp_size)) {
-                std::lock_guard<std::mutex> g(mu);
-                err_msg = j.ss->cat->path + ": page size fields out of bounds";
-                err_flag = 1;
-                break;
-            }
-            size_t payload = size_t(dp->compressed_size) - size_t(dp->def_level_bytes);
-            const uint8_t* src = tmp.data() + in_chunk + dp->def_level_bytes;
-            uint64_t data_off = j.dst_off;  // raw page bytes (post-codec)
-            size_t raw_size = payload;
-            // OPTIONAL column: the levels are decoded, never trusted to the
-            // statistics. lvl = level bytes that open the DEcompressed body
-            // of a compressed v1 page (0 otherwise: def_level_bytes already
-            // skipped them). Zstd pages are looked at after the decompress.
-            static const char* const col_names[4] = {"series_id", "timestamp",
-                                                     "value", "__seq__"};
-            uint32_t lvl = 0;
-            uint32_t n_valid = (uint32_t)j.num_values;
-            auto check_levels = [&](const uint8_t* post, size_t post_len) {
-                std::string why = page_levels(
-                    *dp, j.codec, tmp.data() + in_chunk, post, post_len,
-                    j.bitmap_off ? (uint64_t*)(plan.h_blob + j.bitmap_off)
-                                 : nullptr,
-                    &lvl, &n_valid);
-                if (why.empty() && int64_t(n_valid) != j.num_values) {
-                    const std::string n_null =
-                        std::to_string(j.num_values - int64_t(n_valid)) +
-                        " null(s): ";
-                    if (j.col != 2)
-                        why = n_null + "nulls in a key column are not "
-                                       "supported";
-                    else if (bytes_val)
-                        why = n_null + "nulls in a Binary value column are "
-                                       "not supported";
-                    else if (P->h->update_mode == 1)
-                        why = n_null + "Append mode over null values is not "
-                                       "supported";
-                    else if (dp->encoding != hx::ENC_PLAIN)
-                        why = n_null + "nulls in a dictionary-encoded value "
-                                       "page are not supported (PLAIN only)";
-                    else
-                        j.has_nulls = true;
-                }
-                if (why.empty()) return true;
-                std::lock_guard<std::mutex> g(mu);
-                err_msg = j.ss->cat->path + ": column " + col_names[j.col] +
-                          ": " + why;
-                err_flag = 1;
-                return false;
-            };
-            const bool zstd_page = j.codec == hx::CODEC_ZSTD && dp->is_compressed;
-            if (!j.required && !(zstd_page && dp->levels_in_stream) &&
-                !check_levels(nullptr, 0))
-                break;
-            if (j.codec == hx::CODEC_ZSTD && dp->is_compressed) {
-                // host-side decompress into the blob (staging, untimed)
-                size_t want = size_t(dp->uncompressed_size) -
-                              size_t(dp->def_level_bytes);
-                size_t got = zstd().decompress(plan.h_blob + j.dst_off, want,
-                                               src, payload);
-                if (zstd().is_error(got) || got != want) {
-                    std::lock_guard<std::mutex> g(mu);
-                    err_msg = j.ss->cat->path + ": Zstd page decode failed";
-                    err_flag = 1;
-                    break;
-                }
-                raw_size = want;
-                if (!j.required && dp->levels_in_stream) {
-                    // drop the level block: the body moves to the reserved
-                    // (64-aligned) start, as for a REQUIRED page
-                    if (!check_levels(plan.h_blob + j.dst_off, want)) break;
-                    std::memmove(plan.h_blob + j.dst_off,
-                                 plan.h_blob + j.dst_off + lvl, want - lvl);
-                    raw_size = want - lvl;
-                    lvl = 0;
-                }
-            }
-            // Stored Snappy page (preamble + ONE literal covering the whole
-            // page — what the writer emits for incompressible data): nothing
-            // to decode. The payload goes into the blob verbatim, shifted by
-            // pad so the literal body sits on a 64-byte boundary, and the
-            // column offset points at the body: the scan kernels read it in
-            // place like an uncompressed PLAIN page (no SnappyPageDesc, no
-            // dec space). PLAIN 8-byte columns only; dictionary/DELTA pages
-            // and byte-value stores keep the decoder path.
-            bool stored = false;
-            if (j.codec == hx::CODEC_SNAPPY && dp->is_compressed &&
-                dp->encoding == hx::ENC_PLAIN && !(bytes_val && j.col == 2) &&
-                dp->uncompressed_size >= dp->def_level_bytes) {
-                const uint32_t ulen =
-                    (uint32_t)(size_t(dp->uncompressed_size) -
-                               size_t(dp->def_level_bytes));
-                uint32_t body_off = 0;
-                if (hx_snappy_stored_literal(src, payload, ulen, &body_off)) {
-                    // an OPTIONAL v1 page's literal opens with the level
-                    // block (lvl <= ulen, checked against the page size):
-                    // the PLAIN body behind it is what gets aligned
-                    body_off += lvl;
-                    const size_t pad = (64 - (body_off & 63u)) & 63u;
-                    // reserve = comp_size + 64 >= pad + payload
-                    std::memcpy(plan.h_blob + j.dst_off + pad, src, payload);
-                    data_off = j.dst_off + pad + body_off;
-                    raw_size = ulen - lvl;
-                    lvl = 0;
-                    stored = true;
-                    std::lock_guard<std::mutex> g(mu);
-                    plan.pages_in_place++;
-                    plan.bytes_in_place += raw_size;
-                }
-            }
-            if (!stored && !(j.codec == hx::CODEC_ZSTD && dp->is_compressed))
-                std::memcpy(plan.h_blob + j.dst_off, src, payload);
-            if (!stored && j.codec == hx::CODEC_SNAPPY && dp->is_compressed &&
-                dp->uncompressed_size == dp->def_level_bytes) {
-                raw_size = 0;   // v2 page of nulls only: nothing to decode
-            } else if (!stored && j.codec == hx::CODEC_SNAPPY &&
-                       dp->is_compressed) {
-                std::lock_guard<std::mutex> g(mu);
-                hx::SnappyPageDesc sp{};
-                sp.src_off = j.dst_off;
-                sp.comp_len = (uint32_t)payload;
-                sp.uncomp_len = (uint32_t)(size_t(dp->uncompressed_size) -
-                                           size_t(dp->def_level_bytes));
-                sp.dst_off = hx::OFF_DEC | dec_off;
-                dec_off = align64(dec_off + sp.uncomp_len);
-                plan.snappy_pages.push_back(sp);
-                // the decoder's dst stays 64-aligned; an OPTIONAL v1 page's
-                // body follows its level block there
-                data_off = sp.dst_off + lvl;
-                raw_size = sp.uncomp_len - lvl;
-            }
-
-            if (bytes_val && j.col == 2) {
-                // Binary value column (BytesMergeOperator stores,
-                // operator.rs:47-111): PLAIN BYTE_ARRAY payload stays in
-                // the blob; per-row handles (off << 20 | len) are walked by
-                // k_ba_offsets into the SST's handle array at decode time.
-                // Snappy value pages would decode into the dec blob, which
-                // the handle packing cannot address — rejected loudly
-                // (uncompressed and Zstd, which decompresses in place, OK).
-                if (dp->encoding != hx::ENC_PLAIN ||
-                    (j.codec == hx::CODEC_SNAPPY && dp->is_compressed)) {
-                    std::lock_guard<std::mutex> g(mu);
-                    err_msg = j.ss->cat->path + ": byte value columns "
-                              "support PLAIN uncompressed/Zstd pages only";
-                    err_flag = 1;
-                    break;
-                }
-                std::lock_guard<std::mutex> g(mu);
-                hx::BaPageDesc bp{};
-                bp.src_off = data_off;   // blob byte offset (no flag bit)
-                bp.src_len = raw_size;
-                bp.n_values = (uint32_t)j.num_values;
-                bp.first_row = int64_t(j.ss->bytes_handles / 8) + j.row_base;
-                plan.ba_pages.push_back(bp);
-                j.final_off = hx::OFF_DEC |
-                              (j.ss->bytes_handles + uint64_t(j.row_base) * 8);
-            } else if (dp->encoding == hx::ENC_PLAIN) {
-                // the body holds the present values only
-                if (raw_size != size_t(n_valid) * 8) {
-                    std::lock_guard<std::mutex> g(mu);
-                    err_msg = j.ss->cat->path + ": PLAIN payload size mismatch";
-                    err_flag = 1;
-                    break;
-                }
-                if (lvl || j.has_nulls) {
-                    // body behind a level block in dec (not 8-aligned), or
-                    // packed around nulls: k_expand_optional writes the dense
-                    // column on every decode pass
-                    std::lock_guard<std::mutex> g(mu);
-                    hx::ExpandPageDesc ep{};
-                    ep.src_off = data_off - lvl;
-                    ep.src_len = (uint32_t)(raw_size + lvl);
-                    ep.lvl_bytes = lvl;
-                    ep.n_rows = (uint32_t)j.num_values;
-                    ep.n_valid = n_valid;
-                    ep.bitmap_off = j.has_nulls ? j.bitmap_off : 0;
-                    ep.dst_off = hx::OFF_DEC | dec_off;
-                    dec_off = align64(dec_off + size_t(j.num_values) * 8);
-                    plan.expand_pages.push_back(ep);
-                    if (j.has_nulls) plan.has_nulls = true;
-                    data_off = ep.dst_off;
-                }
-                j.final_off = data_off;
-            } else if (dp->encoding == hx::ENC_DELTA_BINARY_PACKED && j.col != 2) {
-                std::lock_guard<std::mutex> g(mu);
-                hx::DeltaPageDesc dd{};
-                dd.src_off = data_off;
-                dd.src_len = (uint32_t)raw_size;
-                dd.n_values = (uint32_t)j.num_values;
-                if (j.num_values > 8192) {
-                    err_msg = j.ss->cat->path + ": delta page > 8192 values";
-                    err_flag = 1;
-                    break;
-                }
-                dd.dst_off = hx::OFF_DEC | dec_off;
-                dec_off = align64(dec_off + size_t(j.num_values) * 8);
-                plan.delta_pages.push_back(dd);
-                j.final_off = dd.dst_off;
-            } else if ((dp->encoding == hx::ENC_RLE_DICTIONARY ||
-                        dp->encoding == hx::ENC_PLAIN_DICTIONARY) && dictp) {
-                // dict payload was copied at dst_off together with the data
-                // payload (the whole-chunk staging copy keeps page payloads
-                // at their in-chunk offsets) — recompute both offsets
-                std::lock_guard<std::mutex> g(mu);
-                hx::RleDictPageDesc rd{};
-                size_t dict_in_chunk = size_t(dictp->payload_off - j.chunk_start);
-                size_t dict_payload = size_t(dictp->compressed_size);
-                // re-copy the dictionary payload right after the data
-                // payload (raw_size >= payload when Zstd decompressed it)
-                size_t reserve = std::max(size_t(j.comp_size),
-                                          j.codec == hx::CODEC_ZSTD
-                                              ? size_t(j.uncomp_size)
-                                              : size_t(0));
-                size_t dict_dst = j.dst_off +
-                                  ((std::max(raw_size, payload) + 15) &
-                                   ~size_t(15));
-                size_t dict_need = j.codec == hx::CODEC_ZSTD
-                                       ? size_t(dictp->uncompressed_size)
-                                       : dict_payload;
-                if (dict_dst + dict_need > j.dst_off + reserve + 64) {
-                    err_msg = j.ss->cat->path + ": dictionary staging overflow";
-                    err_flag = 1;
-                    break;
-                }
-                uint64_t dict_data_off = dict_dst;
-                uint32_t dict_raw;
-                if (j.codec == hx::CODEC_ZSTD && dictp->is_compressed) {
-                    size_t got = zstd().decompress(
-                        plan.h_blob + dict_dst, dict_need,
-                        tmp.data() + dict_in_chunk, dict_payload);
-                    if (zstd().is_error(got) || got != dict_need) {
-                        err_msg = j.ss->cat->path + ": Zstd dict decode failed";
-                        err_flag = 1;
-                        break;
-                    }
-                    dict_raw = (uint32_t)dict_need;
-                } else {
-                    std::memcpy(plan.h_blob + dict_dst,
-                                tmp.data() + dict_in_chunk, dict_payload);
-                    dict_raw = (uint32_t)dict_payload;
-                }
-                if (j.codec == hx::CODEC_SNAPPY) {
-                    hx::SnappyPageDesc sp{};
-                    sp.src_off = dict_dst;
-                    sp.comp_len = (uint32_t)dict_payload;
-                    sp.uncomp_len = (uint32_t)dictp->uncompressed_size;
-                    sp.dst_off = hx::OFF_DEC | dec_off;
-                    dec_off = align64(dec_off + sp.uncomp_len);
-                    plan.snappy_pages.push_back(sp);
-                    dict_data_off = sp.dst_off;
-                    dict_raw = sp.uncomp_len;
-                }
-                if (dict_raw != (uint32_t)dictp->num_values * 8) {
-                    err_msg = j.ss->cat->path + ": dictionary size mismatch";
-                    err_flag = 1;
-                    break;
-                }
-                rd.dict_off = dict_data_off;
-                rd.dict_n = (uint32_t)dictp->num_values;
-                rd.idx_off = data_off;
-                rd.idx_len = (uint32_t)raw_size;
-                rd.n_values = (uint32_t)j.num_values;
-                rd.dst_off = hx::OFF_DEC | dec_off;
-                dec_off = align64(dec_off + size_t(j.num_values) * 8);
-                plan.rledict_pages.push_back(rd);
-                j.final_off = rd.dst_off;
-            } else {
-                std::lock_guard<std::mutex> g(mu);
-                err_msg = j.ss->cat->path + ": encoding " +
-                          std::to_string(dp->encoding) + " unsupported (round 1)";
+                err_msg = s.msg;
                 err_flag = 1;
                 break;
             }
         }
-        if (last_fd >= 0) close(last_fd);
+        if (fd >= 0) close(fd);
     };
-    unsigned n_threads = std::min<unsigned>(16, std::max(1u, std::thread::hardware_concurrency()));
     {
         std::vector<std::thread> ts;
-        for (unsigned t = 0; t < n_threads; t++) ts.emplace_back(worker);
+        for (auto& b : bundles) ts.emplace_back(worker, std::ref(b));
         for (auto& t : ts) t.join();
     }
     if (err_flag.load()) return fail(HX_ERR_UNSUPPORTED, err_msg);
-
-    // patch RgDesc offsets from job results; build dense copies for overlap
-    plan.rg_valid.assign(plan.rgs.size(), hx::RgValid{0, 0});
-    size_t job_i = 0;
-    size_t rg_i = 0;
-    for (StagedSst* ss : members) {
-        hx::SstDev& sd = plan.ssts[ss->dev_slot];
-        const int n_staged_cols = sd.dense_seq ? 4 : 3;
-        int64_t row_base = 0;
-        for (size_t k = 0; k < ss->rg_idx.size(); k++, rg_i++) {
-            hx::RgDesc& rd = plan.rgs[rg_i];
-            uint64_t offs[4] = {0, 0, 0, 0};
-            for (int c = 0; c < n_staged_cols; c++, job_i++) {
-                offs[c] = jobs[job_i].final_off;
-                if (c == 2 && jobs[job_i].has_nulls)
-                    plan.rg_valid[rg_i].off = jobs[job_i].bitmap_off;
-            }
-            rd.series_off = offs[0];
-            rd.ts_off = offs[1];
-            rd.val_off = offs[2];
-            if (sd.dense_seq) {
-                hx::CopyDesc cq{};
-                cq.src_off = offs[3];
-                cq.dst_off = (sd.dense_seq & hx::OFF_MASK) +
-                             uint64_t(row_base) * 8;
-                cq.n_values = rd.n_rows;
-                plan.copies.push_back(cq);
-            }
-            if (ss->cluster >= 0) {
-                // dense (series, ts) arrays for binary-search dedup
-                hx::CopyDesc cs{};
-                cs.src_off = offs[0];
-                cs.dst_off = (sd.dense_series & hx::OFF_MASK) + uint64_t(row_base) * 8;
-                cs.n_values = rd.n_rows;
-                plan.copies.push_back(cs);
-                hx::CopyDesc ct{};
-                ct.src_off = offs[1];
-                ct.dst_off = (sd.dense_ts & hx::OFF_MASK) + uint64_t(row_base) * 8;
-                ct.n_values = rd.n_rows;
-                plan.copies.push_back(ct);
-            }
-            row_base += rd.n_rows;
-        }
+    auto append = [](auto& dst, const auto& src) {
+        dst.insert(dst.end(), src.begin(), src.end());
+    };
+    for (const hx::StagedPages& b : bundles) {
+        append(plan.snappy_pages, b.snappy);
+        append(plan.expand_pages, b.expand);
+        append(plan.delta_pages, b.delta);
+        append(plan.rledict_pages, b.rledict);
+        append(plan.ba_pages, b.ba);
+        plan.pages_in_place += b.pages_in_place;
+        plan.bytes_in_place += b.bytes_in_place;
     }
-    plan.dec_bytes = dec_off;
+    for (const hx::ChunkResult& r : results)
+        if (r.has_nulls) plan.has_nulls = true;
+    return HX_OK;
+}
 
-    // ---- slice + align row groups across SSTs ----------------------------
-    // SSTs may carry different rows-per-series (time windows of 1 vs 2
-    // points), so the k-th row group of two SSTs can cover very different
-    // series ranges. For the group table's L2/L3 locality under the wave
-    // kernel the unit list is (a) split into ~half-row-group slices and
-    // (b) ordered by FRACTIONAL row position within its SST — units at
-    // the same fraction cover the same series quantile of the shared series
-    // universe. Speed-only: dispatch order is never relied on for
-    // correctness; dedup successor links (next_rg) are remapped.
-    {
-        uint32_t split = 2;   // ~4096-row units
-        if (const char* se = getenv("HX_RG_SPLIT"))
-            split = (uint32_t)strtoul(se, nullptr, 10);
-        if (split < 1) split = 1;
-        const size_t n_old = plan.rgs.size();
-        std::vector<hx::RgDesc> sliced;
-        std::vector<hx::RgValid> sliced_valid;
-        std::vector<int32_t> new_first(n_old);
-        std::vector<int32_t> last_slice(n_old);
-        for (size_t i = 0; i < n_old; i++) {
-            const hx::RgDesc& rd = plan.rgs[i];
-            const uint32_t ssize =
-                std::max<uint32_t>(1024, (rd.n_rows + split - 1) / split);
-            new_first[i] = (int32_t)sliced.size();
-            for (uint32_t start = 0; start < rd.n_rows; start += ssize) {
-                hx::RgDesc sl = rd;
-                sl.series_off = rd.series_off + uint64_t(start) * 8;
-                sl.ts_off = rd.ts_off + uint64_t(start) * 8;
-                sl.val_off = rd.val_off + uint64_t(start) * 8;
-                sl.n_rows = std::min(ssize, rd.n_rows - start);
-                sl.row_base = rd.row_base + start;
-                // same bitmap, later bit: a slice need not start on a word
-                sliced_valid.push_back({plan.rg_valid[i].off, start});
-                sl.next_rg = (start + ssize < rd.n_rows)
-                                 ? (int32_t)sliced.size() + 1
-                                 : rd.next_rg;  // old id; remapped below
-                last_slice[i] = (int32_t)sliced.size();
-                sliced.push_back(sl);
-            }
-        }
-        for (size_t i = 0; i < n_old; i++) {
-            int32_t nx = plan.rgs[i].next_rg;
-            sliced[last_slice[i]].next_rg = nx >= 0 ? new_first[nx] : -1;
-        }
-        // fractional position of each slice within its SST's staged rows
-        std::vector<int64_t> sst_rows(plan.ssts.size(), 0);
-        for (const auto& sl : sliced) {
-            int64_t end = sl.row_base + sl.n_rows;
-            if (end > sst_rows[sl.sst_id]) sst_rows[sl.sst_id] = end;
-        }
-        std::vector<uint32_t> order(sliced.size());
-        for (size_t i = 0; i < sliced.size(); i++) order[i] = (uint32_t)i;
-        std::vector<double> frac(sliced.size());
-        for (size_t i = 0; i < sliced.size(); i++)
-            frac[i] = sst_rows[sliced[i].sst_id]
-                          ? double(sliced[i].row_base) /
-                                double(sst_rows[sliced[i].sst_id])
-                          : 0.0;
-        // order purely by fractional position: concurrently resident blocks
-        // then share one narrow series window across ALL SSTs, keeping the
-        // group table's hot lines cache-resident (measured 1.8x on the wave
-        // kernel vs size-class-primary ordering)
-        std::stable_sort(order.begin(), order.end(),
-                         [&](uint32_t a, uint32_t b) { return frac[a] < frac[b]; });
-        std::vector<int32_t> inv(sliced.size());
-        for (size_t i = 0; i < sliced.size(); i++) inv[order[i]] = (int32_t)i;
-        std::vector<hx::RgDesc> reordered(sliced.size());
-        std::vector<hx::RgValid> reordered_valid(sliced.size());
-        for (size_t i = 0; i < sliced.size(); i++) {
-            reordered[i] = sliced[order[i]];
-            reordered_valid[i] = sliced_valid[order[i]];
-            if (reordered[i].next_rg >= 0)
-                reordered[i].next_rg = inv[reordered[i].next_rg];
-        }
-        plan.rgs.swap(reordered);
-        plan.rg_valid.swap(reordered_valid);
-        if (!plan.has_nulls) plan.rg_valid.clear();   // nothing to upload
-    }
+// RgDesc offsets from the chunk results, then the unit list the kernels run
+// over (stage_chunk.h has both; HX_RG_SPLIT sets the slices per row group).
+static void slice_and_order(DevPlan& plan,
+                            const std::vector<hx::ChunkResult>& results) {
+    hx::patch_rg_offsets(plan.rgs, plan.rg_valid, plan.ssts, results,
+                         plan.copies);
+    uint32_t split = 2;   // ~4096-row units
+    if (const char* se = getenv("HX_RG_SPLIT"))
+        split = (uint32_t)strtoul(se, nullptr, 10);
+    hx::SstRgLists lists;
+    hx::slice_and_order(plan.rgs, plan.rg_valid, plan.ssts.size(), split,
+                        lists);
+    plan.h_sst_rgs.swap(lists.rgs);
+    plan.h_sst_rg_off.swap(lists.off);
+    plan.h_sst_rg_cnt.swap(lists.cnt);
+    if (!plan.has_nulls) plan.rg_valid.clear();   // nothing to upload
+}
 
-    // per-SST rg lists in row order (series-range kernel): the
-    // fractional reorder above scrambles plan.rgs, so the range kernel
-    // walks SSTs through these index lists instead
-    {
-        const size_t n = plan.rgs.size();
-        std::vector<uint32_t> idx(n);
-        for (size_t i = 0; i < n; i++) idx[i] = (uint32_t)i;
-        std::sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) {
-            if (plan.rgs[a].sst_id != plan.rgs[b].sst_id)
-                return plan.rgs[a].sst_id < plan.rgs[b].sst_id;
-            return plan.rgs[a].row_base < plan.rgs[b].row_base;
-        });
-        plan.h_sst_rgs.assign(idx.begin(), idx.end());
-        plan.h_sst_rg_off.assign(plan.ssts.size(), 0);
-        plan.h_sst_rg_cnt.assign(plan.ssts.size(), 0);
-        for (size_t i = 0; i < n; i++) {
-            uint32_t sid = plan.rgs[idx[i]].sst_id;
-            if (plan.h_sst_rg_cnt[sid] == 0)
-                plan.h_sst_rg_off[sid] = (int32_t)i;
-            plan.h_sst_rg_cnt[sid]++;
-        }
-    }
-
-    // ---- upload ----------------------------------------------------------
+static hx_status upload_plan(DevPlan& plan) {
     HIP_TRY(hipSetDevice(plan.device));
     if (!plan.stream) HIP_TRY(hipStreamCreate(&plan.stream));
     if (plan.blob_bytes) {
@@ -1221,14 +668,40 @@ static hx_status stage_device(hx_prepared* P, DevPlan& plan,
     HIP_TRY(upload(plan.d_sst_rg_cnt, plan.h_sst_rg_cnt));
     HIP_TRY(hipMalloc((void**)&plan.d_counters, 6 * sizeof(unsigned long long)));
     HIP_TRY(hipStreamSynchronize(plan.stream));
+    return HX_OK;
+}
+
+static void free_host_blob(DevPlan& plan) {
+    if (!plan.h_blob) return;
+    if (plan.h_blob_pinned) hipHostFree(plan.h_blob);
+    else free(plan.h_blob);
+    plan.h_blob = nullptr;
+}
+
+static hx_status stage_device(hx_prepared* P, DevPlan& plan,
+                              std::vector<StagedSst*>& members) {
+    std::vector<PageJob> jobs;
+    std::atomic<size_t> dec{layout_jobs(P, plan, members, jobs)};
+    if (plan.h_blob == nullptr && plan.blob_bytes > 0) {
+        if (hipHostMalloc((void**)&plan.h_blob, plan.blob_bytes,
+                          hipHostMallocDefault) == hipSuccess) {
+            plan.h_blob_pinned = true;
+        } else {
+            plan.h_blob = (uint8_t*)malloc(plan.blob_bytes);
+            plan.h_blob_pinned = false;
+            if (!plan.h_blob) return fail(HX_ERR_IO, "staging alloc failed");
+        }
+    }
+    std::vector<hx::ChunkResult> results(jobs.size());
+    hx_status st = stage_chunks(plan, jobs, results, dec);
+    if (st != HX_OK) return st;
+    plan.dec_bytes = dec.load();
+    slice_and_order(plan, results);
+    st = upload_plan(plan);
     // staging buffer no longer needed once resident in HBM (frees up to
     // 12 GB of pinned host memory per rank for the 8-GPU runs)
-    if (plan.h_blob) {
-        if (plan.h_blob_pinned) hipHostFree(plan.h_blob);
-        else free(plan.h_blob);
-        plan.h_blob = nullptr;
-    }
-    return HX_OK;
+    if (st == HX_OK) free_host_blob(plan);
+    return st;
 }
 
 extern "C" hx_status hx_prepare(hx_handle* h, const hx_scan_spec* spec,
@@ -1248,7 +721,12 @@ extern "C" hx_status hx_prepare(hx_handle* h, const hx_scan_spec* spec,
         if (d < 0 || d >= n_gpu)
             return fail(HX_ERR_INVALID, "bad device id");
 
-    auto P = std::make_unique<hx_prepared>();
+    // every early return below frees what was built so far (pinned blob,
+    // device buffers and streams of the plans already staged)
+    struct PreparedFree {
+        void operator()(hx_prepared* p) const { hx_prepared_free(p); }
+    };
+    std::unique_ptr<hx_prepared, PreparedFree> P(new hx_prepared);
     P->h = h;
     // retain ONLY the fields the exec paths read (the time range): the
     // caller owns preds/ssts/projection and may free them right after this
@@ -1393,7 +871,8 @@ extern "C" hx_status hx_prepare(hx_handle* h, const hx_scan_spec* spec,
         }
         if (!plan.cluster_members.empty()) {
             HIP_TRY(hipSetDevice(plan.device));
-            if (plan.d_members) HIP_TRY(hipFree(plan.d_members));
+            if (plan.d_members) hipFree(plan.d_members);
+            plan.d_members = nullptr;
             HIP_TRY(hipMalloc((void**)&plan.d_members,
                               plan.cluster_members.size() * sizeof(int32_t)));
             HIP_TRY(hipMemcpy(plan.d_members, plan.cluster_members.data(),
@@ -1413,10 +892,7 @@ extern "C" void hx_prepared_free(hx_prepared* P) {
     if (!P) return;
     for (auto& plan : P->plans) {
         hipSetDevice(plan.device);
-        if (plan.h_blob) {
-            if (plan.h_blob_pinned) hipHostFree(plan.h_blob);
-            else free(plan.h_blob);
-        }
+        free_host_blob(plan);
         for (void* p : {(void*)plan.d_blob, (void*)plan.d_dec, (void*)plan.d_rgs,
                         (void*)plan.d_ssts, (void*)plan.d_clusters,
                         (void*)plan.d_members, (void*)plan.d_delta,
@@ -1427,7 +903,8 @@ extern "C" void hx_prepared_free(hx_prepared* P) {
                         (void*)plan.t_bstore, (void*)plan.d_counters,
                         (void*)plan.d_sset, (void*)plan.d_sst_rgs,
                         (void*)plan.d_sst_rg_off, (void*)plan.d_sst_rg_cnt,
-                        (void*)plan.d_range_bounds, (void*)plan.d_bound_rows})
+                        (void*)plan.d_range_bounds, (void*)plan.d_bound_rows,
+                        plan.d_scratch, plan.d_sort_temp})
             if (p) hipFree(p);
         for (auto ev : plan.ev)
             if (ev) hipEventDestroy(ev);
@@ -2453,68 +1930,35 @@ extern "C" hx_status hx_debug_page_levels(
     if (row_group < 0 || size_t(row_group) >= cat.rgs.size())
         return fail(HX_ERR_INVALID, "row group out of range");
     const ChunkRef& cr = cat.rgs[row_group].cols[col];
-    if (cr.comp_size <= 0 || cr.comp_size > (int64_t)1 << 31)
-        return fail(HX_ERR_FORMAT, cat.path + ": implausible chunk size");
-    std::vector<uint8_t> tmp(cr.comp_size);
     int fd = open(path, O_RDONLY);
     if (fd < 0) return fail(HX_ERR_IO, "open " + cat.path);
-    const ssize_t got = pread(fd, tmp.data(), tmp.size(), cr.chunk_start);
+    std::vector<uint8_t> tmp;
+    hx::StageStatus s = hx::read_chunk(fd, cat.path, cr, tmp);
     close(fd);
-    if (got != (ssize_t)tmp.size())
-        return fail(HX_ERR_IO, "chunk read " + cat.path);
-    std::vector<hx::PageDesc> pages;
-    try {
-        pages = hx::walk_pages(tmp.data(), tmp.size(), cr.chunk_start,
-                               cr.num_values, !cr.required, cr.codec);
-    } catch (const std::exception& e) {
-        return fail(HX_ERR_FORMAT, cat.path + ": " + e.what());
+    if (!s.ok()) return fail(s.st, s.msg);
+    // the chunk is staged as hx_prepare stages it, into a slot of its own
+    std::vector<uint8_t> slot_mem(hx::chunk_reserve(cr));
+    hx::ChunkSlot slot;
+    slot.base = slot_mem.data();
+    slot.cap = slot_mem.size();
+    slot.bitmap = bitmap_out;
+    slot.bitmap_cap = size_t(cap_words) * 8;
+    hx::ChunkRole role;
+    role.col = col;
+    role.bytes_value = cat.bytes_value;
+    std::atomic<size_t> dec{0};
+    hx::StagedPages pages;
+    hx::ChunkResult res;
+    s = hx::stage_chunk(tmp.data(), cr, role, slot, dec, pages, res);
+    if (!s.ok()) return fail(s.st, cat.path + ": " + s.msg);
+    *n_rows = cr.num_values;
+    *n_valid = res.n_valid;
+    *level_bytes = int32_t(res.level_bytes);
+    if (cr.required && bitmap_out) {
+        for (size_t i = 0; i < (size_t(cr.num_values) + 63) / 64; i++)
+            bitmap_out[i] = 0;
+        hx_bitmap_set_range(bitmap_out, 0, uint64_t(cr.num_values));
     }
-    const hx::PageDesc* dp = nullptr;
-    int n_data = 0;
-    for (const auto& p : pages)
-        if (p.page_type == 0 || p.page_type == 3) {
-            dp = &p;
-            n_data++;
-        }
-    if (n_data != 1 || dp->num_values != cr.num_values || dp->num_values < 0)
-        return fail(HX_ERR_UNSUPPORTED,
-                    cat.path + ": expected one data page per chunk");
-    const size_t words = (size_t(dp->num_values) + 63) / 64;
-    if (bitmap_out && cap_words < words)
-        return fail(HX_ERR_INVALID, "bitmap capacity too small");
-    *n_rows = dp->num_values;
-    if (cr.required) {
-        *n_valid = dp->num_values;
-        *level_bytes = 0;
-        if (bitmap_out) {
-            for (size_t i = 0; i < words; i++) bitmap_out[i] = 0;
-            hx_bitmap_set_range(bitmap_out, 0, uint64_t(dp->num_values));
-        }
-        return HX_OK;
-    }
-    const uint8_t* page = tmp.data() + size_t(dp->payload_off - cr.chunk_start);
-    std::vector<uint8_t> post;
-    if (dp->levels_in_stream && cr.codec == hx::CODEC_ZSTD) {
-        if (!zstd().ok)
-            return fail(HX_ERR_UNSUPPORTED, cat.path + ": Zstd pages but "
-                                            "libzstd.so.1 is not loadable");
-        post.resize(size_t(dp->uncompressed_size));
-        const size_t n = zstd().decompress(post.data(), post.size(), page,
-                                           size_t(dp->compressed_size));
-        if (zstd().is_error(n) || n != post.size())
-            return fail(HX_ERR_FORMAT, cat.path + ": Zstd page decode failed");
-    } else if (dp->levels_in_stream && cr.codec != hx::CODEC_SNAPPY) {
-        return fail(HX_ERR_UNSUPPORTED, cat.path + ": codec unsupported "
-                                        "(uncompressed, Snappy and Zstd)");
-    }
-    uint32_t in_stream = 0, nv = 0;
-    const std::string why =
-        page_levels(*dp, cr.codec, page, post.empty() ? nullptr : post.data(),
-                    post.size(), bitmap_out, &in_stream, &nv);
-    if (!why.empty())
-        return fail(HX_ERR_FORMAT, cat.path + ": column " + column + ": " + why);
-    *n_valid = nv;
-    *level_bytes = int32_t(in_stream ? in_stream : dp->def_level_bytes);
     return HX_OK;
 }
 

@@ -26,10 +26,12 @@ extern "C" hx_status hx_debug_snappy_decompress(
     const uint32_t* uncomp_lens, uint32_t n, uint8_t* out,
     const uint64_t* out_offs, uint64_t* n_errors);
 
-// Test hook (exported, not part of the public C-ABI, no GPU needed): run the
-// staging parse of one column chunk — chunk read, page walk, the codec step
-// that exposes the definition levels, levels -> bitmap — and return what
-// staging would use. column is one of series_id, timestamp, value, __seq__.
+// Test hook (exported, not part of the public C-ABI, no GPU needed): stage
+// one column chunk exactly as hx_prepare does — hx::read_chunk and
+// hx::stage_chunk (stage_chunk.h), into a scratch slot of the reserved size,
+// Overwrite mode — and return what staging used; a chunk staging refuses
+// (nulls in a key column, ...) is refused here with the same message.
+// column is one of series_id, timestamp, value, __seq__.
 // bitmap_out (may be NULL) receives (n_rows + 63) / 64 LSB-first words;
 // cap_words is its capacity. *level_bytes is the size of the level block in
 // front of the page body (0 for a REQUIRED column).

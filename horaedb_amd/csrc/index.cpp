@@ -237,24 +237,19 @@ extern "C" hx_status hx_index_query(hx_handle* h, const hx_tag_pred* preds,
                     return set_error(HX_ERR_IO, path + ": chunk read");
                 }
                 const int col_i = which == 0 ? ck : which == 1 ? cv : ct;
-                std::vector<hx::PageDesc> pages;
+                hx::ChunkPages pages;
+                bool one_page = false;
                 try {
-                    pages = hx::walk_pages(chunk.data(), chunk.size(),
-                                           cc.chunk_start(), cc.num_values,
-                                           !m.columns[col_i].required,
-                                           cc.codec);
+                    one_page = hx::select_pages(
+                        chunk.data(), chunk.size(), cc.chunk_start(),
+                        cc.num_values, !m.columns[col_i].required, cc.codec,
+                        &pages);
                 } catch (const std::exception& e) {
                     close(fd);
                     return set_error(HX_ERR_FORMAT, path + ": " + e.what());
                 }
-                const hx::PageDesc* dp = nullptr;
-                int nd = 0;
-                for (auto& p : pages)
-                    if (p.page_type == 0 || p.page_type == 3) {
-                        dp = &p;
-                        nd++;
-                    }
-                if (nd != 1 || !dp || dp->num_values != rg.num_rows) {
+                const hx::PageDesc* dp = &pages.data;
+                if (!one_page || dp->num_values != rg.num_rows) {
                     close(fd);
                     return set_error(HX_ERR_FORMAT,
                                      path + ": expected one data page per "

@@ -265,4 +265,22 @@ std::vector<PageDesc> walk_pages(const uint8_t* buf, size_t len,
     return pages;
 }
 
+bool select_pages(const uint8_t* buf, size_t len, int64_t base_off,
+                  int64_t num_values, bool optional_col, int32_t codec,
+                  ChunkPages* out) {
+    int n_data = 0;
+    *out = ChunkPages{};
+    for (const PageDesc& p :
+         walk_pages(buf, len, base_off, num_values, optional_col, codec)) {
+        if (p.page_type == 0 || p.page_type == 3) {
+            out->data = p;
+            n_data++;
+        } else if (p.page_type == 2) {
+            out->dict = p;
+            out->has_dict = true;
+        }
+    }
+    return n_data == 1 && out->data.num_values == num_values;
+}
+
 }  // namespace hx

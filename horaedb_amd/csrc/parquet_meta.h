@@ -89,6 +89,19 @@ std::vector<PageDesc> walk_pages(const uint8_t* buf, size_t len,
                                  bool optional_col = false,
                                  int32_t codec = 0);
 
+// The layout contract every reader here shares: a column chunk holds exactly
+// one v1/v2 data page whose value count is the chunk's, plus at most one
+// dictionary page. Walks the chunk (walk_pages: throws on malformed headers)
+// and picks the two; returns false when the chunk does not keep the contract.
+struct ChunkPages {
+    PageDesc data{};
+    PageDesc dict{};
+    bool has_dict = false;
+};
+bool select_pages(const uint8_t* buf, size_t len, int64_t base_off,
+                  int64_t num_values, bool optional_col, int32_t codec,
+                  ChunkPages* out);
+
 // little-endian i64 from an 8-byte statistics value
 int64_t stat_i64(const std::string& s);
 
