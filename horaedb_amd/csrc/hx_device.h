@@ -71,7 +71,7 @@ struct ClusterDev {
 //   state-word: {state u32, pad, series, bucket, sum, cnt[, min, max]},
 //     stride 48/64; state: 0 empty, 1 claim in flight, 2 ready (key words
 //     valid).
-// min/max are ordered-u64 mapped f64 (bit-exact min/max).
+// min/max are f64_ordered u64 words (IEEE 754 totalOrder, bits kept).
 struct AggTable {
     uint32_t  mask;            // slots-1 (power of two)
     uint8_t*  slab;

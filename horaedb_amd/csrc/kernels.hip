@@ -30,8 +30,14 @@ __device__ __forceinline__ uint64_t mix64(uint64_t x) {
     return x ^ (x >> 31);
 }
 
-// monotone f64 -> u64 map: preserves total order, so u64 atomicMin/Max give
-// bit-exact f64 min/max.
+// monotone f64 -> u64 map onto IEEE 754 totalOrder (-NaN < -inf < ... < -0 <
+// +0 < ... < +inf < +NaN, NaNs by payload): u64 min/max of these words, by
+// atomicMin/Max or in registers, pick one operand and ordered_f64 returns
+// its 64 bits unchanged — NaN payload, signalling bit and the sign of zero
+// included. Every min/max reduction runs on these words, none
+// on fmin/fmax (which drop NaN, may quiet it, and are free in the sign of
+// zero). Identities: ~0 for min, 0 for max — neither is the image of a
+// double a reduction could lose to (the slab initialisers use the same).
 __device__ __forceinline__ unsigned long long f64_ordered(double v) {
     unsigned long long u = __double_as_longlong(v);
     return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
@@ -105,8 +111,9 @@ __device__ __forceinline__ uint64_t row_seq(const AggParams& P,
 // indexed bucket mode) bucket b's row of the slot's dense accumulator rows
 __device__ __forceinline__ void keycas_add(const AggParams& P, uint32_t i,
                                            int64_t b, double vsum,
-                                           unsigned long long cnt, double mn,
-                                           double mx) {
+                                           unsigned long long cnt,
+                                           unsigned long long mn,
+                                           unsigned long long mx) {
     uint8_t* slot;
     uint32_t off8, off16, off24, off32;
     if (P.n_buckets) {  // direct-indexed bucket row of this series slot
@@ -128,9 +135,9 @@ __device__ __forceinline__ void keycas_add(const AggParams& P, uint32_t i,
     if (P.ops & (HXK_COUNT | HXK_AVG))
         atomicAdd((unsigned long long*)(slot + off16), cnt);
     if (P.ops & HXK_MIN)
-        atomicMin((unsigned long long*)(slot + off24), f64_ordered(mn));
+        atomicMin((unsigned long long*)(slot + off24), mn);
     if (P.ops & HXK_MAX)
-        atomicMax((unsigned long long*)(slot + off32), f64_ordered(mx));
+        atomicMax((unsigned long long*)(slot + off32), mx);
 }
 
 // Fast claim path (AoS slab): slot i = {key, sum, cnt[, min, max]} in one
@@ -142,7 +149,8 @@ __device__ __forceinline__ void keycas_add(const AggParams& P, uint32_t i,
 __device__ __forceinline__ void agg_update_keycas(const AggParams& P, uint64_t s,
                                                   int64_t b, double vsum,
                                                   unsigned long long cnt,
-                                                  double mn, double mx,
+                                                  unsigned long long mn,
+                                                  unsigned long long mx,
                                                   uint32_t hint_i = 0xFFFFFFFFu,
                                                   uint64_t hint_k = 0) {
     const uint32_t stride = P.table.stride;
@@ -234,7 +242,8 @@ k_init_slab(uint8_t* slab, uint32_t n_slots, uint32_t stride) {
 __device__ __forceinline__ void agg_update(const AggParams& P, uint64_t s,
                                            int64_t b, double vsum,
                                            unsigned long long cnt,
-                                           double mn, double mx,
+                                           unsigned long long mn,
+                                           unsigned long long mx,
                                            uint32_t hint_i = 0xFFFFFFFFu,
                                            uint64_t hint_k = 0) {
     if (P.key_claim) {
@@ -283,9 +292,9 @@ __device__ __forceinline__ void agg_update(const AggParams& P, uint64_t s,
             if (P.ops & (HXK_COUNT | HXK_AVG))
                 atomicAdd((unsigned long long*)(slot + 32), cnt);
             if (P.ops & HXK_MIN)
-                atomicMin((unsigned long long*)(slot + 40), f64_ordered(mn));
+                atomicMin((unsigned long long*)(slot + 40), mn);
             if (P.ops & HXK_MAX)
-                atomicMax((unsigned long long*)(slot + 48), f64_ordered(mx));
+                atomicMax((unsigned long long*)(slot + 48), mx);
             return;
         }
         i = (i + 1) & P.table.mask;
@@ -344,14 +353,15 @@ __device__ __forceinline__ bool row_alive(const AggParams& P, const RgDesc& rg,
 struct WinResult {
     uint64_t s;
     int64_t b;
-    double vv, mn, mx;
+    double vv;
+    unsigned long long mn, mx;   // f64_ordered words
     unsigned long long c;
     bool head;
     uint32_t hint_i;    // early-probed slot index (key-claim tables)
     uint64_t hint_k;    // its key value at probe time
 };
 
-template <bool NULLS>
+template <bool NULLS, bool MM>
 __device__ __forceinline__ void scan_window(const AggParams& P,
                                             const RgDesc& rg, uint32_t rgi,
                                             const SstDev& sst,
@@ -410,8 +420,12 @@ __device__ __forceinline__ void scan_window(const AggParams& P,
     }
     unsigned long long c = alive ? 1ull : 0ull;
     double vv = alive ? v : 0.0;
-    double mn = alive ? v : HUGE_VAL;
-    double mx = alive ? v : -HUGE_VAL;
+    // ordered words with the ordered identities: a dead lane must lose to
+    // every live value, +NaN in a min and -NaN in a max included. Only the
+    // MM instances (min or max requested) carry them through the reduction.
+    const unsigned long long ov = f64_ordered(v);
+    unsigned long long mn = (MM && alive) ? ov : ~0ull;
+    unsigned long long mx = (MM && alive) ? ov : 0ull;
     if (!NULLS) my_matched += c;
     // issue the table probe NOW: its L3 latency hides under the cross-lane
     // reduction, and a hit skips the dependent probe load in agg_update
@@ -431,14 +445,18 @@ __device__ __forceinline__ void scan_window(const AggParams& P,
         const long long b2 = __shfl_down((long long)b, d, 64);
         const double v2 = __shfl_down(vv, d, 64);
         const unsigned long long c2 = __shfl_down(c, d, 64);
-        const double mn2 = __shfl_down(mn, d, 64);
-        const double mx2 = __shfl_down(mx, d, 64);
         done = done || (lane + d >= 64) || s2 != s || b2 != b;
         if (head && !done) {
             vv += v2;
             c += c2;
-            mn = fmin(mn, mn2);
-            mx = fmax(mx, mx2);
+        }
+        if (MM) {
+            const unsigned long long mn2 = __shfl_down(mn, d, 64);
+            const unsigned long long mx2 = __shfl_down(mx, d, 64);
+            if (head && !done) {
+                mn = mn2 < mn ? mn2 : mn;
+                mx = mx2 > mx ? mx2 : mx;
+            }
         }
         if (__all(done)) break;
     }
@@ -457,7 +475,7 @@ __device__ __forceinline__ void scan_window(const AggParams& P,
 // dependent table-update chains (L3 probe + atomics) overlap — the kernel
 // is memory-latency-bound (SQ_WAIT_ANY 76%) at full occupancy, so the
 // lever is per-wave memory-level parallelism.
-template <bool NULLS>
+template <bool NULLS, bool MM>
 __global__ void __launch_bounds__(256)
 k_scan_agg(AggParams P) {
     unsigned long long my_matched = 0;
@@ -491,12 +509,12 @@ k_scan_agg(AggParams P) {
             WinResult A, B;
             B.c = 0;
             B.head = false;
-            scan_window<NULLS>(P, rg, rgi, sst, S, T, V, base, n, lane,
-                               my_matched, A);
+            scan_window<NULLS, MM>(P, rg, rgi, sst, S, T, V, base, n, lane,
+                                   my_matched, A);
             const uint32_t base2 = base + blockDim.x;
             if (base2 < n)
-                scan_window<NULLS>(P, rg, rgi, sst, S, T, V, base2, n, lane,
-                                   my_matched, B);
+                scan_window<NULLS, MM>(P, rg, rgi, sst, S, T, V, base2, n,
+                                       lane, my_matched, B);
             const bool upA = A.head && A.c > 0;
             const bool upB = B.head && B.c > 0;
             if (upA && upB) {  // two independent chains: overlap them
@@ -646,7 +664,9 @@ __device__ __forceinline__ bool lds_update(uint64_t* lkey, double* lsum,
                                            unsigned long long* lmin,
                                            unsigned long long* lmax,
                                            uint32_t ne, uint64_t sv, double v,
-                                           uint32_t cnt, double mn, double mx,
+                                           uint32_t cnt,
+                                           unsigned long long mn,
+                                           unsigned long long mx,
                                            uint32_t i, uint64_t pre) {
 #pragma unroll 1
     for (uint32_t probes = 0; probes < ne; probes++) {
@@ -659,8 +679,8 @@ __device__ __forceinline__ bool lds_update(uint64_t* lkey, double* lsum,
             atomicAdd(&lsum[i], v);
             atomicAdd(&lcnt[i], cnt);
             if (MM) {
-                atomicMin(&lmin[i], f64_ordered(mn));
-                atomicMax(&lmax[i], f64_ordered(mx));
+                atomicMin(&lmin[i], mn);
+                atomicMax(&lmax[i], mx);
             }
             return true;
         }
@@ -901,21 +921,31 @@ k_scan_agg_range2(AggParams P, RangeAux R, RangeOut O) {
                         if (a0) a0 = row_valid(P, (uint32_t)rgi, r0);
                         if (a1) a1 = row_valid(P, (uint32_t)rgi, r1);
                     }
-                    // in-lane pair merge, then direct LDS updates
+                    // in-lane pair merge, then direct LDS updates; min/max
+                    // travel as ordered words, mapped only for rows that
+                    // survived (only the MM instances read them, so the
+                    // others compute none of this)
                     const bool merge = a0 && a1 && (s0 == s1);
                     if (merge) {
+                        const unsigned long long o0 = f64_ordered(v0);
+                        const unsigned long long o1 = f64_ordered(v1);
+                        const bool lt = o1 < o0;
                         lost |= !lds_update<MM>(
                             lkey, lsum, lcnt, lmin, lmax, ne, s0, v0 + v1,
-                            2u, fmin(v0, v1), fmax(v0, v1), iA, preA);
+                            2u, lt ? o1 : o0, lt ? o0 : o1, iA, preA);
                     } else {
-                        if (a0)
+                        if (a0) {
+                            const unsigned long long o = f64_ordered(v0);
                             lost |= !lds_update<MM>(
                                 lkey, lsum, lcnt, lmin, lmax, ne, s0, v0,
-                                1u, v0, v0, iA, preA);
-                        if (a1)
+                                1u, o, o, iA, preA);
+                        }
+                        if (a1) {
+                            const unsigned long long o = f64_ordered(v1);
                             lost |= !lds_update<MM>(
                                 lkey, lsum, lcnt, lmin, lmax, ne, s1, v1,
-                                1u, v1, v1, iB, preB);
+                                1u, o, o, iB, preB);
+                        }
                     }
                 }
                 pos++;
@@ -2701,11 +2731,22 @@ hipError_t launch_scan_agg(hipStream_t s, const AggParams& p, uint32_t grid,
                            bool nulls) {
     if (grid == 0) grid = p.n_rgs > 65535 ? 65535 : (p.n_rgs ? p.n_rgs : 1);
     // NULLS is a launch-level template parameter, as for the range kernel:
-    // a wrapper around one shared body costs the null-off instance 3 VGPRs
-    if (nulls)
-        hipLaunchKernelGGL(k_scan_agg<true>, dim3(grid), dim3(256), 0, s, p);
+    // a wrapper around one shared body costs the null-off instance 3 VGPRs.
+    // MM likewise: the ordered-word min/max reduction is compiled into the
+    // instances a min/max query launches and into no other.
+    const bool mm = (p.ops & (HXK_MIN | HXK_MAX)) != 0;
+    if (nulls && mm)
+        hipLaunchKernelGGL((k_scan_agg<true, true>), dim3(grid), dim3(256),
+                           0, s, p);
+    else if (nulls)
+        hipLaunchKernelGGL((k_scan_agg<true, false>), dim3(grid), dim3(256),
+                           0, s, p);
+    else if (mm)
+        hipLaunchKernelGGL((k_scan_agg<false, true>), dim3(grid), dim3(256),
+                           0, s, p);
     else
-        hipLaunchKernelGGL(k_scan_agg<false>, dim3(grid), dim3(256), 0, s, p);
+        hipLaunchKernelGGL((k_scan_agg<false, false>), dim3(grid), dim3(256),
+                           0, s, p);
     return hipGetLastError();
 }
 

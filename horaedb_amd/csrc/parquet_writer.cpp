@@ -145,8 +145,9 @@ std::vector<uint8_t> page_header(int32_t n_values, int32_t payload) {
     return std::move(w.buf);
 }
 
+// Returns whether the chunk gets statistics at all.
 template <typename T>
-void minmax_bytes(const T* v, int64_t n, std::string& mn, std::string& mx) {
+bool minmax_bytes(const T* v, int64_t n, std::string& mn, std::string& mx) {
     T lo = v[0], hi = v[0];
     for (int64_t i = 1; i < n; i++) {
         if (v[i] < lo) lo = v[i];
@@ -154,6 +155,34 @@ void minmax_bytes(const T* v, int64_t n, std::string& mn, std::string& mx) {
     }
     mn.assign((const char*)&lo, 8);
     mx.assign((const char*)&hi, 8);
+    return true;
+}
+
+// DOUBLE statistics follow parquet.thrift's ColumnOrder rules for floating
+// point: NaN never enters min/max (a chunk of nothing but NaN carries no
+// statistics), and a zero bound is written min = -0.0 / max = +0.0 so a
+// reader that distinguishes the signs cannot prune the other zero away.
+bool minmax_bytes(const double* v, int64_t n, std::string& mn,
+                  std::string& mx) {
+    bool any = false;
+    double lo = 0.0, hi = 0.0;
+    for (int64_t i = 0; i < n; i++) {
+        const double x = v[i];
+        if (x != x) continue;
+        if (!any) {
+            lo = hi = x;
+            any = true;
+        } else {
+            if (x < lo) lo = x;
+            if (x > hi) hi = x;
+        }
+    }
+    if (!any) return false;
+    if (lo == 0.0) lo = -0.0;
+    if (hi == 0.0) hi = 0.0;
+    mn.assign((const char*)&lo, 8);
+    mx.assign((const char*)&hi, 8);
+    return true;
 }
 
 }  // namespace
@@ -204,10 +233,10 @@ std::string write_metric_sst(const std::string& path, const uint64_t* series,
                     minmax_bytes((const int64_t*)data[c], rows, m.mn, m.mx);
                     break;
                 case 2:
-                    minmax_bytes((const double*)data[c], rows, m.mn, m.mx);
+                    m.has_stats = minmax_bytes((const double*)data[c], rows,
+                                               m.mn, m.mx);
                     break;
             }
-            m.has_stats = true;
             if (fwrite(hdr.data(), 1, hdr.size(), f) != hdr.size())
                 return fail("write failed");
             if (fwrite(data[c], 8, rows, f) != size_t(rows))
@@ -332,8 +361,8 @@ std::string write_table_sst(const std::string& path, const WriterCol* cols,
                 body = (const uint8_t*)wc.data + base * 8;
                 body_len = size_t(rows) * 8;
                 if (wc.physical == 5)
-                    minmax_bytes((const double*)wc.data + base, rows, m.mn,
-                                 m.mx);
+                    m.has_stats = minmax_bytes((const double*)wc.data + base,
+                                               rows, m.mn, m.mx);
                 else if (wc.converted == 14)
                     minmax_bytes((const uint64_t*)wc.data + base, rows, m.mn,
                                  m.mx);

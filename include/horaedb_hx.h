@@ -100,7 +100,34 @@ enum {
  * by a newer value) and counts in hx_exec_stats.rows_matched. The aggregates
  * run over the non-null survivors: sum/min/max/avg ignore nulls and count
  * counts values. A group all of whose surviving values are null is not
- * emitted (the result table has no validity channel). */
+ * emitted (the result table has no validity channel).
+ *
+ * Value domain (every f64 bit pattern is data: NaN of either sign and any
+ * payload — the Prometheus stale marker 0x7FF0000000000002 is a signalling
+ * NaN — signed zeros, infinities, subnormals):
+ *   min / max  IEEE 754 totalOrder over the surviving non-null values:
+ *              -NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN, NaNs of one
+ *              sign ordered by payload (Rust's f64::total_cmp). The 64 bits
+ *              of the chosen value are returned unchanged: payload,
+ *              signalling bit and the sign of zero. On one device the
+ *              result does not depend on where a row sits in its file.
+ *              EXCEPTION, more than one device: the host merge of the
+ *              per-device partials still combines vmin/vmax with
+ *              std::min/std::max on doubles, so for a group whose rows are
+ *              split across devices a NaN may be dropped or kept and the
+ *              sign of a zero chosen by the order of the partials.
+ *   sum / avg  NaN (payload unspecified) if the group holds a NaN or both
+ *              infinities; else the infinity it holds; else the finite sum
+ *              of an unspecified order of additions (an overflowing one is
+ *              an infinity). Subnormal terms and partial sums are kept on
+ *              every route (no flush to zero). The sign of a zero sum is
+ *              unspecified (accumulators start at +0.0).
+ *   count      a NaN is a value and counts; only nulls drop out.
+ *   hx_scan, hx_compact, hx_compact_files, hx_write: every value's 64 bits
+ *              come back unchanged. Files written here carry DOUBLE
+ *              statistics as parquet-format demands: no NaN in min/max (a
+ *              row group of nothing but NaN carries none), a zero bound
+ *              written min = -0.0 / max = +0.0. */
 typedef struct {
     uint32_t ops;         /* OR of HX_AGG_*  (over the value column) */
     int64_t  bucket_ms;   /* 0: group by series_id; >0: by (series_id,

@@ -22,6 +22,8 @@
 """
 import numpy as np
 
+from .value_domain import group_max, group_min
+
 MERGE_LAST = "last"      # UpdateMode::Overwrite -> LastValueOperator (read.rs:482-492)
 MERGE_APPEND = "append"  # UpdateMode::Append   -> BytesMergeOperator
 
@@ -175,7 +177,8 @@ def scan_agg(ssts, ts_range, series_set=None, bucket_ms=0,
     Returns dict of 1-D arrays sorted by (series_id[, bucket]):
           series_id, bucket?, sum, count, vmin, vmax, avg (requested ops).
     Sums accumulate in ts order within each group (deterministic reference
-    order for the 1e-9-relative GPU comparison).
+    order for the 1e-9-relative GPU comparison). vmin/vmax follow IEEE 754
+    totalOrder and carry the chosen value's bits (oracle/value_domain.py).
     """
     lo, hi = ts_range
     sset = None
@@ -218,9 +221,9 @@ def scan_agg(ssts, ts_range, series_set=None, bucket_ms=0,
     if ops & (AGG_COUNT | AGG_AVG):
         res["count"] = (kend - kstart).astype(np.uint64)
     if ops & AGG_MIN:
-        res["vmin"] = np.minimum.reduceat(v, kstart)
+        res["vmin"] = group_min(v, kstart)   # totalOrder, bits kept
     if ops & AGG_MAX:
-        res["vmax"] = np.maximum.reduceat(v, kstart)
+        res["vmax"] = group_max(v, kstart)
     if ops & AGG_AVG:
         res["avg"] = res["sum"] / res["count"]
     if not (ops & AGG_SUM):

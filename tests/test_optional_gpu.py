@@ -21,6 +21,7 @@ import pytest
 
 from horaedb_amd import (AGG_SUM, AGG_COUNT, AGG_MIN, AGG_MAX, AGG_AVG,
                          HxError)
+from oracle.value_domain import group_max, group_min
 
 pytestmark = pytest.mark.gpu
 
@@ -144,8 +145,8 @@ def expected_agg(ssts, ts_range=FULL, series_in=None, bucket_ms=0):
     if len(starts):
         exp["count"] = np.diff(np.append(starts, len(series))).astype(np.uint64)
         exp["sum"] = np.add.reduceat(value, starts)
-        exp["vmin"] = np.minimum.reduceat(value, starts)
-        exp["vmax"] = np.maximum.reduceat(value, starts)
+        exp["vmin"] = group_min(value, starts)   # totalOrder, bits kept
+        exp["vmax"] = group_max(value, starts)
     else:
         exp["count"] = np.empty(0, np.uint64)
         exp["sum"] = exp["vmin"] = exp["vmax"] = np.empty(0)

@@ -297,6 +297,297 @@ def middle_range(manifest, frac=0.5):
     return lo, hi
 
 
+# ---------------------------------------------------------------------------
+# Value-domain datasets (tests/test_value_domain_*.py): the f64 values a
+# metric engine meets beyond U[0,1) — NaN of either sign (quiet, signalling,
+# the Prometheus stale marker), signed zeros, infinities, subnormals,
+# DBL_MAX — placed so every one of them meets every lane and pair slot of
+# the aggregate kernels as the first, an inner and the last row of its
+# group. Values travel as uint64 bit patterns throughout.
+# ---------------------------------------------------------------------------
+VD_SPECIAL = [
+    ("+0", 0x0000000000000000), ("-0", 0x8000000000000000),
+    ("+inf", 0x7FF0000000000000), ("-inf", 0xFFF0000000000000),
+    ("+qnan", 0x7FF8000000000000), ("-qnan", 0xFFF8000000000000),
+    ("stale", 0x7FF0000000000002),      # Prometheus stale marker (signalling)
+    ("+nan_max", 0x7FFFFFFFFFFFFFFF),
+    ("+denorm_min", 0x0000000000000001), ("-denorm_min", 0x8000000000000001),
+    ("+min_normal", 0x0010000000000000), ("-min_normal", 0x8010000000000000),
+    ("+dbl_max", 0x7FEFFFFFFFFFFFFF), ("-dbl_max", 0xFFEFFFFFFFFFFFFF),
+    ("+1", 0x3FF0000000000000), ("-1", 0xBFF0000000000000),
+]
+VD_BITS = np.array([b for _, b in VD_SPECIAL], dtype=np.uint64)
+_VD_DBL_MAX = {i for i, (n, _) in enumerate(VD_SPECIAL) if "dbl_max" in n}
+VD_NAN = {i for i, (n, _) in enumerate(VD_SPECIAL)
+          if "nan" in n or n == "stale"}
+
+VD_T0 = 1_000_000            # ts of row j of an ordinary group: T0 + j*STEP
+VD_STEP = 1_000
+VD_MAX_RUN = 5
+VD_RANGE = (VD_T0, VD_T0 + VD_MAX_RUN * VD_STEP)   # holds every group row;
+#   the filler rows of the ts-range identity traps lie outside it
+VD_BUCKET_MS = 2 * VD_STEP   # splits a 5-row group into rows 01 | 23 | 4
+VD_BOUNDARY = 8192           # the default row-group size
+
+
+def _f2b(x):
+    return np.asarray(x, dtype=np.float64).view(np.uint64)
+
+
+def vd_class_of(bits):
+    """Index into VD_SPECIAL of each bit pattern, -1 for any other value."""
+    bits = np.asarray(bits, dtype=np.uint64)
+    cls = np.full(len(bits), -1, dtype=np.int64)
+    for i, b in enumerate(VD_BITS):
+        cls[bits == b] = i
+    return cls
+
+
+def _vd_filler(rng, n):
+    """Mixed-sign ordinary values, |x| in [1e-3, 1e3]."""
+    mag = 10.0 ** rng.uniform(-3, 3, n)
+    return _f2b(mag * rng.choice([-1.0, 1.0], n))
+
+
+def _vd_cover_groups(rng):
+    """Groups (lists of bit patterns, run length 1..5) that put every class
+    of VD_SPECIAL at every row position mod 128 as the first, an inner and
+    the last row of a group, assuming the first group starts at a row that
+    is a multiple of 128. At most one |x| = DBL_MAX per group: two of them
+    make the sum's overflow depend on the order of the additions."""
+    n_cls = len(VD_SPECIAL)
+    need = np.ones((n_cls, 3, 128), dtype=bool)   # class, role, position
+    order = rng.permutation(n_cls)
+
+    def roles(j, L):
+        r = []
+        if j == 0:
+            r.append(0)
+        if j == L - 1:
+            r.append(2)
+        return r or [1]
+
+    groups, r = [], 0
+    while need.any():
+        # the run length that serves the most open (role, position) pairs
+        best, best_score = 1, -1.0
+        for L in range(1, VD_MAX_RUN + 1):
+            score = sum(need[:, ro, (r + j) % 128].any()
+                        for j in range(L) for ro in roles(j, L)) / L
+            if score > best_score + 1e-12:
+                best, best_score = L, score
+        L = best
+        g, has_max = [], False
+        for j in range(L):
+            pos = (r + j) % 128
+            pick = -1
+            for c in order:
+                if has_max and c in _VD_DBL_MAX:
+                    continue
+                if any(need[c, ro, pos] for ro in roles(j, L)):
+                    pick = int(c)
+                    break
+            if pick < 0:
+                g.append(int(_vd_filler(rng, 1)[0]))
+                continue
+            for ro in roles(j, L):
+                need[pick, ro, pos] = False
+            has_max |= pick in _VD_DBL_MAX
+            g.append(int(VD_BITS[pick]))
+            order = np.roll(order, 1)
+        groups.append(g)
+        r += L
+    return groups
+
+
+def _vd_fixed_groups():
+    """Hand-written groups: cancellation, same-sign overflow, all-subnormal
+    (every partial sum of those is a representable subnormal, so their sum
+    is exact under any order)."""
+    d = 5e-324
+    vals = [
+        [1e16, 1.0, -1e16, 3.0],
+        [1e100, -1e100, 1e-100],
+        [-1e16, 1e16, 1.0, -1.0, 2.5],
+        [0.1, 0.2, -0.3],
+        [1e308, 1e308, 1e308],             # +inf
+        [-1e308, -1e308, -1e308],          # -inf
+        [d, d, d, d, d],
+        [3 * d, -d, 7 * d],
+        [-d, -2 * d, -4 * d, -8 * d],
+        [2.0 ** -1030, 2.0 ** -1040, -(2.0 ** -1050), d],
+        [1023 * d],
+        [2.0 ** -1023, 2.0 ** -1024, 2.0 ** -1025, 2.0 ** -1026],
+    ]
+    return [[int(b) for b in _f2b(v)] for v in vals]
+
+
+def vd_base_rows(seed=0, sentinel_series=False):
+    """The one-SST value-domain table: dict of row arrays sorted by
+    (series, ts) — series u64, ts i64, bits u64, kind i8 per row
+    (0 padding, 1 coverage, 2 fixed, 3 identity trap).
+    Layout: mixed-sign padding groups (a multiple of 128 rows, sized so the
+    file passes VD_BOUNDARY and a coverage group holding a special straddles
+    it), the coverage groups, the fixed groups, then the two ts-range
+    identity traps: a series whose only row inside VD_RANGE is +NaN (-NaN in
+    the second), between rows of the same series outside the range.
+    sentinel_series: the last fixed group gets series id 2**64-1 (a store
+    the one-CAS key claim cannot serve) and the traps are left out."""
+    rng = np.random.default_rng(seed)
+    cover = _vd_cover_groups(rng)
+    starts = np.cumsum([0] + [len(g) for g in cover])
+    n_cover = int(starts[-1])
+    pad = None
+    lo = -(-(VD_BOUNDARY + 64 - n_cover) // 128) * 128
+    for p in range(max(lo, 0), max(lo, 0) + 128 * 64, 128):
+        for g, s in zip(cover, starts):
+            if s + p < VD_BOUNDARY < s + p + len(g) and \
+                    (vd_class_of(g) >= 0).any():
+                pad = p
+                break
+        if pad is not None:
+            break
+    assert pad is not None, "no coverage group straddles the boundary"
+    groups, kinds = [], []
+    left, L = pad, 1
+    while left > 0:
+        k = min(L, left)
+        groups.append([int(b) for b in _vd_filler(rng, k)])
+        kinds.append(0)
+        left -= k
+        L = L % VD_MAX_RUN + 1
+    groups += cover
+    kinds += [1] * len(cover)
+    fixed = _vd_fixed_groups()
+    groups += fixed
+    kinds += [2] * len(fixed)
+    n_groups = len(groups) + 2
+    stride = (2 ** 63) // n_groups     # ids spread over half the u64 range
+    series, ts, bits, kind = [], [], [], []
+    for k, (g, kd) in enumerate(zip(groups, kinds)):
+        sid = (k + 1) * stride + (k * 7919) % 1000
+        if sentinel_series and k == len(groups) - 1:
+            sid = 2 ** 64 - 1
+        for j, b in enumerate(g):
+            series.append(sid)
+            ts.append(VD_T0 + j * VD_STEP)
+            bits.append(b)
+            kind.append(kd)
+    if not sentinel_series:
+        out_ts = [VD_RANGE[0] - 2 * VD_STEP, VD_RANGE[0] - VD_STEP,
+                  VD_T0 + 2 * VD_STEP, VD_RANGE[1], VD_RANGE[1] + VD_STEP]
+        for t, nan in enumerate((0x7FF8000000000000, 0xFFF8000000000000)):
+            sid = (len(groups) + 1 + t) * stride + 13
+            fill = _vd_filler(rng, 5)
+            for j in range(5):
+                series.append(sid)
+                ts.append(out_ts[j])
+                bits.append(nan if j == 2 else int(fill[j]))
+                kind.append(3)
+    return {"series": np.array(series, dtype=np.uint64),
+            "ts": np.array(ts, dtype=np.int64),
+            "bits": np.array(bits, dtype=np.uint64),
+            "kind": np.array(kind, dtype=np.int8)}
+
+
+def vd_overwrite_rows(base, seed=1, nullable=False):
+    """The newer SST of the two-file variants: it rewrites, by PK, every
+    second special row of the coverage groups with a finite value and every
+    second ordinary row (padding and coverage filler) with a special (never
+    |x| = DBL_MAX, see _vd_cover_groups), so dedup has to decide by key
+    alone. It also carries the superseded-row identity traps: two new series
+    whose rows sit in BOTH files; the older file's middle row is +NaN (-NaN),
+    the newer file rewrites the four rows around it and not the NaN.
+    nullable: the rewriting trap rows are null, so the NaN is the series'
+    only surviving value.
+    Returns (older, newer): row dicts like vd_base_rows' plus 'null'."""
+    rng = np.random.default_rng(seed)
+    cls = vd_class_of(base["bits"])
+    grp = base["kind"]
+    special = np.flatnonzero((cls >= 0) & (grp == 1))[::2]
+    plain = np.flatnonzero((cls < 0) & (grp <= 1))[::2]
+    ok = np.array([i for i in range(len(VD_SPECIAL))
+                   if i not in _VD_DBL_MAX])
+    take = np.sort(np.concatenate([special, plain]))
+    new_bits = base["bits"][take].copy()
+    is_sp = np.isin(take, special)
+    new_bits[is_sp] = _vd_filler(rng, int(is_sp.sum()))
+    new_bits[~is_sp] = VD_BITS[ok[np.arange(int((~is_sp).sum())) % len(ok)]]
+    older = {k: v.copy() for k, v in base.items()}
+    newer = {"series": base["series"][take], "ts": base["ts"][take],
+             "bits": new_bits, "kind": base["kind"][take]}
+    # superseded-row traps, after every other series
+    top = int(base["series"].max())
+    o_rows, n_rows = [], []
+    for t, nan in enumerate((0x7FF8000000000000, 0xFFF8000000000000)):
+        sid = top + 1000 * (t + 1)
+        fill = _vd_filler(rng, 10)
+        for j in range(5):
+            tsj = VD_T0 + j * VD_STEP
+            o_rows.append((sid, tsj, nan if j == 2 else int(fill[j])))
+            if j != 2:
+                n_rows.append((sid, tsj, int(fill[5 + j])))
+    for d, rows in ((older, o_rows), (newer, n_rows)):
+        d["series"] = np.concatenate(
+            [d["series"], np.array([r[0] for r in rows], dtype=np.uint64)])
+        d["ts"] = np.concatenate(
+            [d["ts"], np.array([r[1] for r in rows], dtype=np.int64)])
+        d["bits"] = np.concatenate(
+            [d["bits"], np.array([r[2] for r in rows], dtype=np.uint64)])
+        d["kind"] = np.concatenate(
+            [d["kind"], np.full(len(rows), 3, dtype=np.int8)])
+    older["null"] = np.zeros(len(older["series"]), dtype=bool)
+    newer["null"] = np.zeros(len(newer["series"]), dtype=bool)
+    if nullable:
+        # ~30 % nulls; a null next to every third NaN row; one series null
+        # throughout; traps: the rewriting rows null, the NaN row never
+        all_null = base["series"][np.flatnonzero(grp == 1)[40]]
+        for d in (older, newer):
+            n = len(d["series"])
+            m = rng.random(n) < 0.3
+            nan_rows = np.flatnonzero(np.isin(vd_class_of(d["bits"]),
+                                              list(VD_NAN)))[::3]
+            m[np.clip(nan_rows[0::2] - 1, 0, n - 1)] = True
+            m[np.clip(nan_rows[1::2] + 1, 0, n - 1)] = True
+            m[nan_rows] = False
+            m[d["series"] == all_null] = True
+            trap = d["kind"] == 3
+            m[trap] = False
+            if d is newer:
+                m[trap & (d["series"] > top)] = True
+            d["null"] = m
+    return older, newer
+
+
+def vd_coverage(series, bits, row_group):
+    """Where the special classes sit in one (series, ts)-sorted file:
+    (missing, straddles). missing lists every (class name, role, position
+    mod 128) that does not occur, role being first/inner/last row of a
+    run-length 1..5 group; straddles counts special values inside groups
+    that cross a multiple of row_group."""
+    series = np.asarray(series, dtype=np.uint64)
+    n = len(series)
+    cls = vd_class_of(bits)
+    first = np.ones(n, dtype=bool)
+    first[1:] = series[1:] != series[:-1]
+    last = np.ones(n, dtype=bool)
+    last[:-1] = first[1:]
+    gid = np.cumsum(first) - 1
+    gstart = np.flatnonzero(first)[gid]
+    glen = np.bincount(gid)[gid]
+    seen = np.zeros((len(VD_SPECIAL), 3, 128), dtype=bool)
+    rows = np.flatnonzero((cls >= 0) & (glen <= VD_MAX_RUN))
+    pos = rows % 128
+    seen[cls[rows[first[rows]]], 0, pos[first[rows]]] = True
+    inner = ~first[rows] & ~last[rows]
+    seen[cls[rows[inner]], 1, pos[inner]] = True
+    seen[cls[rows[last[rows]]], 2, pos[last[rows]]] = True
+    missing = [(VD_SPECIAL[c][0], ("first", "inner", "last")[ro], int(p))
+               for c, ro, p in zip(*np.nonzero(~seen))]
+    crosses = (gstart // row_group) != ((gstart + glen - 1) // row_group)
+    return missing, int((crosses & (cls >= 0)).sum())
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("out_dir")
