@@ -9,6 +9,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 enum : int {
     HX_LVL_OK = 0,
@@ -174,3 +175,81 @@ static inline long hx_snappy_prefix(const uint8_t* src, size_t n, uint8_t* out,
     }
     return long(done);
 }
+
+// ---------------------------------------------------------------------------
+// Write side (DESIGN §2 / §4 kernel 1d): the inverse of the above for the
+// native writer. Host-only; <vector> is the one extra dependency.
+// ---------------------------------------------------------------------------
+
+namespace hx {
+
+// Append the v1 level block of one page of a flat OPTIONAL column to `out`:
+// u32 LE length, then RLE/bit-packed hybrid runs at bit width 1.
+// bitmap_words: (n_rows + 63) / 64 LSB-first words, bits at and above n_rows
+// zero, n_valid of them set. A page without nulls is ONE RLE run of 1s (the
+// 6/7/8-byte block of a page of <64 / <8192 / 8192 rows), a page of nothing
+// but nulls one RLE run of 0s; anything else is ONE bit-packed run whose
+// payload is the first ceil(n_rows / 8) bitmap bytes verbatim — the LSB-first
+// bitmap is the 1-bit bit-packed layout, and the zero pad bits of the last
+// group are what the format allows a final run.
+static inline void encode_def_levels(const uint64_t* bitmap_words,
+                                     uint32_t n_rows, uint32_t n_valid,
+                                     std::vector<uint8_t>& out) {
+    const size_t at = out.size();
+    out.insert(out.end(), 4, uint8_t(0));
+    auto varint = [&](uint64_t v) {
+        while (v >= 0x80) {
+            out.push_back(uint8_t(v) | 0x80);
+            v >>= 7;
+        }
+        out.push_back(uint8_t(v));
+    };
+    if (n_valid == n_rows || n_valid == 0) {
+        varint(uint64_t(n_rows) << 1);
+        out.push_back(n_valid ? 1 : 0);
+    } else {
+        const uint32_t n_bytes = (n_rows + 7) / 8;
+        varint((uint64_t(n_bytes) << 1) | 1u);
+        for (uint32_t b = 0; b < n_bytes; b++)
+            out.push_back(uint8_t(bitmap_words[b >> 3] >> ((b & 7u) * 8u)));
+    }
+    const uint32_t len = uint32_t(out.size() - at - 4);
+    for (int b = 0; b < 4; b++) out[at + b] = uint8_t(len >> (8 * b));
+}
+
+// Host twin of kernel 1d (k_pack_optional), same contract: output row i of n
+// is source row perm[i] (i when perm is null) of n_src; valid_bits is an
+// LSB-first bitmap over SOURCE rows (null: all present). Per row group g of
+// row_group rows (a multiple of 64): bitmap_out + g * (row_group / 64)
+// receives row_group / 64 words (bits at and above the group's row count
+// zero), packed_out + g * row_group the group's present values in row order,
+// n_valid_out[g] their number. A perm entry >= n_src is counted in the
+// return value and its row written as null.
+static inline uint64_t pack_optional_host(
+    const uint64_t* values, const uint8_t* valid_bits, const uint32_t* perm,
+    uint64_t n_src, uint64_t n, uint64_t row_group, uint64_t* packed_out,
+    uint64_t* bitmap_out, uint32_t* n_valid_out) {
+    const uint64_t wpg = row_group / 64;
+    uint64_t errors = 0;
+    for (uint64_t g = 0, row0 = 0; row0 < n; g++, row0 += row_group) {
+        const uint64_t rows = n - row0 < row_group ? n - row0 : row_group;
+        uint64_t* bm = bitmap_out + g * wpg;
+        for (uint64_t w = 0; w < wpg; w++) bm[w] = 0;
+        uint32_t k = 0;
+        for (uint64_t r = 0; r < rows; r++) {
+            const uint64_t p = perm ? perm[row0 + r] : row0 + r;
+            if (p >= n_src) {
+                errors++;
+                continue;
+            }
+            if (valid_bits && !((valid_bits[p >> 3] >> (p & 7u)) & 1u))
+                continue;
+            bm[r >> 6] |= 1ull << (r & 63u);
+            packed_out[row0 + k++] = values[p];
+        }
+        n_valid_out[g] = k;
+    }
+    return errors;
+}
+
+}  // namespace hx

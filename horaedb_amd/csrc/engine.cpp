@@ -93,6 +93,9 @@ struct hx_handle {
     int32_t update_mode = 0;             // 0 Overwrite / 1 Append
                                          // (config.rs:166-172)
     bool bytes_value = false;            // value column is BYTE_ARRAY
+    int32_t nullable_values = 0;         // writer setting: 1 = every SST this
+                                         // handle writes declares `value`
+                                         // OPTIONAL (hx_set_nullable_values)
     std::vector<CatSst> ssts;            // ascending seq
     std::vector<hx_sst_desc> find_out;   // scratch for hx_find_ssts
 };
@@ -264,6 +267,20 @@ extern "C" hx_status hx_set_update_mode(hx_handle* h, int32_t mode) {
                     "Append mode needs a Binary value column "
                     "(BytesMergeOperator, operator.rs:47-111)");
     h->update_mode = mode;
+    return HX_OK;
+}
+
+// Writer setting (no reference counterpart: the reference's writer always
+// declares every column nullable). 0: files as before, REQUIRED columns, and
+// null values are refused on the write side. 1: `value` is written OPTIONAL
+// and nulls are kept by hx_write_nullable, hx_compact and hx_compact_files.
+extern "C" hx_status hx_set_nullable_values(hx_handle* h, int32_t on) {
+    if (!h || (on != 0 && on != 1))
+        return fail(HX_ERR_INVALID, "nullable values: 0 off / 1 on");
+    if (on && h->bytes_value)
+        return fail(HX_ERR_UNSUPPORTED,
+                    "nullable values need an f64 value column");
+    h->nullable_values = on;
     return HX_OK;
 }
 
@@ -2023,6 +2040,72 @@ extern "C" hx_status hx_debug_snappy_decompress(
     return HX_OK;
 }
 
+extern "C" hx_status hx_debug_pack_optional(
+    const uint64_t* values, const uint64_t* valid_words,
+    const uint8_t* valid_bits, const uint32_t* perm, uint32_t n_src,
+    uint32_t n, uint32_t row_group, uint64_t* packed_out,
+    uint64_t* bitmap_out, uint32_t* n_valid_out, uint64_t* n_errors) {
+    if (!n_errors || (valid_words && valid_bits) || (n_src && !values) ||
+        (n && (!packed_out || !bitmap_out || !n_valid_out)))
+        return fail(HX_ERR_INVALID, "bad argument");
+    if (row_group == 0 || row_group % 64)
+        return fail(HX_ERR_INVALID, "row_group is not a multiple of 64");
+    *n_errors = 0;
+    if (n == 0) return HX_OK;
+    const size_t n_groups = (size_t(n) + row_group - 1) / row_group;
+    const size_t bm_words = n_groups * (row_group / 64);
+    const size_t valid_bytes =
+        valid_words ? size_t(n_src) * 8 : valid_bits ? (size_t(n_src) + 7) / 8
+                                                     : 0;
+    struct DevBufs {
+        void* p[7] = {};
+        ~DevBufs() {
+            for (void* q : p)
+                if (q) (void)hipFree(q);
+        }
+    } dev;
+    // every buffer exactly as large as the contract says it is
+    HIP_TRY(hipMalloc(&dev.p[0], std::max<size_t>(size_t(n_src) * 8, 8)));
+    HIP_TRY(hipMalloc(&dev.p[1], std::max<size_t>(valid_bytes, 8)));
+    HIP_TRY(hipMalloc(&dev.p[2], size_t(n) * 4));
+    HIP_TRY(hipMalloc(&dev.p[3], size_t(n) * 8));
+    HIP_TRY(hipMalloc(&dev.p[4], bm_words * 8));
+    HIP_TRY(hipMalloc(&dev.p[5], n_groups * 4));
+    HIP_TRY(hipMalloc(&dev.p[6], 8));
+    if (n_src)
+        HIP_TRY(hipMemcpy(dev.p[0], values, size_t(n_src) * 8,
+                          hipMemcpyHostToDevice));
+    if (valid_bytes)
+        HIP_TRY(hipMemcpy(dev.p[1],
+                          valid_words ? (const void*)valid_words
+                                      : (const void*)valid_bits,
+                          valid_bytes, hipMemcpyHostToDevice));
+    if (perm)
+        HIP_TRY(hipMemcpy(dev.p[2], perm, size_t(n) * 4,
+                          hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(dev.p[3], 0xEE, size_t(n) * 8));
+    HIP_TRY(hipMemset(dev.p[4], 0xEE, bm_words * 8));
+    HIP_TRY(hipMemset(dev.p[5], 0xEE, n_groups * 4));
+    HIP_TRY(hipMemset(dev.p[6], 0, 8));
+    HIP_TRY(hx::launch_pack_optional(
+        nullptr, (const unsigned long long*)dev.p[0],
+        valid_bytes ? dev.p[1] : nullptr, valid_bits != nullptr,
+        perm ? (const uint32_t*)dev.p[2] : nullptr, n_src, n, row_group,
+        (unsigned long long*)dev.p[3], (uint64_t*)dev.p[4],
+        (uint32_t*)dev.p[5], (unsigned long long*)dev.p[6]));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(packed_out, dev.p[3], size_t(n) * 8,
+                      hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(bitmap_out, dev.p[4], bm_words * 8,
+                      hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(n_valid_out, dev.p[5], n_groups * 4,
+                      hipMemcpyDeviceToHost));
+    unsigned long long errs = 0;
+    HIP_TRY(hipMemcpy(&errs, dev.p[6], 8, hipMemcpyDeviceToHost));
+    *n_errors = errs;
+    return HX_OK;
+}
+
 extern "C" hx_status hx_scan_agg(hx_handle* h, const hx_scan_spec* spec,
                                  const hx_agg_spec* agg,
                                  const hx_device_set* devs,
@@ -2298,21 +2381,82 @@ extern "C" hx_status hx_write_sst(const char* path, const uint64_t* series,
     return HX_OK;
 }
 
+namespace {
+
+const int64_t kRowGroup = 8192;   // rows per row group of every SST written
+
+// A value column in the nullable writer's row-group-major form (kernel 1d /
+// pack_optional_host output), on the host.
+struct PackedValues {
+    std::vector<uint64_t> packed, bitmap;
+    std::vector<uint32_t> n_valid;
+    void resize(int64_t n, int64_t row_group) {
+        const size_t n_groups = size_t((n + row_group - 1) / row_group);
+        packed.resize(size_t(n));
+        bitmap.resize(n_groups * size_t(row_group / 64));
+        n_valid.resize(n_groups);
+    }
+    hx::NullableValues view() const {
+        return {packed.data(), bitmap.data(), n_valid.data()};
+    }
+};
+
+// number of zero bits among the first n of an LSB-first bitmap
+int64_t count_nulls(const uint8_t* validity, int64_t n) {
+    if (!validity) return 0;
+    int64_t ones = 0;
+    for (int64_t b = 0; b < n / 8; b++) ones += __builtin_popcount(validity[b]);
+    if (n % 8)
+        ones += __builtin_popcount(validity[n / 8] & ((1u << (n % 8)) - 1u));
+    return n - ones;
+}
+
+}  // namespace
+
+extern "C" hx_status hx_write_sst_nullable(
+    const char* path, const uint64_t* series, const int64_t* ts,
+    const double* value, const uint8_t* validity, uint64_t seq,
+    int64_t n_rows, int64_t row_group) {
+    if (!path || !series || !ts || !value || n_rows <= 0 || row_group <= 0)
+        return fail(HX_ERR_INVALID, "bad argument");
+    if (row_group % 64)
+        return fail(HX_ERR_INVALID, "row_group is not a multiple of 64");
+    PackedValues pv;
+    pv.resize(n_rows, row_group);
+    hx::pack_optional_host((const uint64_t*)value, validity, nullptr,
+                           (uint64_t)n_rows, (uint64_t)n_rows,
+                           (uint64_t)row_group, pv.packed.data(),
+                           pv.bitmap.data(), pv.n_valid.data());
+    std::string err = hx::write_metric_sst_nullable(
+        path, series, ts, pv.view(), nullptr, seq, n_rows, row_group);
+    if (!err.empty()) return fail(HX_ERR_IO, err);
+    return HX_OK;
+}
+
 // GPU ingest sort (stable by (series, ts); equal PKs keep input order):
 // two stable LSD radix passes over a u32 permutation — ts (sign-biased),
 // then series — then a device gather and one D2H. Returns false on any HIP
-// error so the caller falls back to the host sort.
+// error so the caller falls back to the host sort. With `pv` (nullable
+// writer) the validity bitmap is uploaded as it is, n / 8 bytes, the gather
+// takes series and ts only, and kernel 1d packs the values by the same
+// permutation; v2 is not written.
 static bool gpu_sort_batch(const uint64_t* series, const int64_t* ts,
                            const double* value, int64_t n,
                            std::vector<uint64_t>& s2, std::vector<int64_t>& t2,
-                           std::vector<double>& v2) {
+                           std::vector<double>& v2,
+                           const uint8_t* validity = nullptr,
+                           PackedValues* pv = nullptr) {
     hipStream_t s = nullptr;
     uint8_t* dev = nullptr;
     void* d_temp = nullptr;
     size_t temp_cap = 0;
     const size_t N = (size_t)n;
+    const size_t n_groups = (N + kRowGroup - 1) / kRowGroup;
+    const size_t bm_words = n_groups * (kRowGroup / 64);
     // layout: series, ts, value, keys_a, keys_b, dst(3N), perm a/b/c
+    // [, validity bitmap, output bitmaps, n_valid, error count]
     size_t bytes = N * 8 * 8 + N * 4 * 3 + 256;
+    if (pv) bytes += (N + 7) / 8 + 8 + bm_words * 8 + n_groups * 4 + 8 + 16;
     bool ok = hipMalloc((void**)&dev, bytes) == hipSuccess;
     auto fail_out = [&]() {
         if (d_temp) (void)hipFree(d_temp);
@@ -2350,24 +2494,55 @@ static bool gpu_sort_batch(const uint64_t* series, const int64_t* ts,
     const unsigned long long* srcs[3] = {
         (const unsigned long long*)d_series, (const unsigned long long*)d_ts,
         (const unsigned long long*)d_val};
-    GS_TRY(hx::launch_gather_multi(s, srcs, 3, pc, d_dst, (uint32_t)N));
     std::vector<uint64_t> host(3 * N);
-    GS_TRY(hipMemcpyAsync(host.data(), d_dst, 3 * N * 8,
-                          hipMemcpyDeviceToHost, s));
-    GS_TRY(hipStreamSynchronize(s));
+    if (pv) {
+        uint8_t* d_vbits = carve((N + 7) / 8, 1);
+        uint64_t* d_bm = (uint64_t*)carve(bm_words, 8);
+        uint32_t* d_nv = (uint32_t*)carve(n_groups, 4);
+        unsigned long long* d_err = (unsigned long long*)carve(1, 8);
+        if (validity)
+            GS_TRY(hipMemcpyAsync(d_vbits, validity, (N + 7) / 8,
+                                  hipMemcpyHostToDevice, s));
+        GS_TRY(hipMemsetAsync(d_err, 0, 8, s));
+        GS_TRY(hx::launch_gather_multi(s, srcs, 2, pc, d_dst, (uint32_t)N));
+        GS_TRY(hx::launch_pack_optional(
+            s, (const unsigned long long*)d_val, validity ? d_vbits : nullptr,
+            true, pc, (uint32_t)N, (uint32_t)N, (uint32_t)kRowGroup,
+            d_dst + 2 * N, d_bm, d_nv, d_err));
+        pv->resize(n, kRowGroup);
+        unsigned long long errs = 0;
+        GS_TRY(hipMemcpyAsync(host.data(), d_dst, 3 * N * 8,
+                              hipMemcpyDeviceToHost, s));
+        GS_TRY(hipMemcpyAsync(pv->bitmap.data(), d_bm, bm_words * 8,
+                              hipMemcpyDeviceToHost, s));
+        GS_TRY(hipMemcpyAsync(pv->n_valid.data(), d_nv, n_groups * 4,
+                              hipMemcpyDeviceToHost, s));
+        GS_TRY(hipMemcpyAsync(&errs, d_err, 8, hipMemcpyDeviceToHost, s));
+        GS_TRY(hipStreamSynchronize(s));
+        if (errs) return fail_out();   // a sort permutation out of range
+        std::memcpy(pv->packed.data(), host.data() + 2 * N, N * 8);
+    } else {
+        GS_TRY(hx::launch_gather_multi(s, srcs, 3, pc, d_dst, (uint32_t)N));
+        GS_TRY(hipMemcpyAsync(host.data(), d_dst, 3 * N * 8,
+                              hipMemcpyDeviceToHost, s));
+        GS_TRY(hipStreamSynchronize(s));
+        std::memcpy(v2.data(), host.data() + 2 * N, N * 8);
+    }
 #undef GS_TRY
     std::memcpy(s2.data(), host.data(), N * 8);
     std::memcpy(t2.data(), host.data() + N, N * 8);
-    std::memcpy(v2.data(), host.data() + 2 * N, N * 8);
     if (d_temp) (void)hipFree(d_temp);
     (void)hipFree(dev);
     return true;
 }
 
-extern "C" hx_status hx_write(hx_handle* h, const uint64_t* series,
-                              const int64_t* ts, const double* value,
-                              int64_t n, int32_t enable_check,
-                              uint64_t* out_seq) {
+// hx_write and hx_write_nullable. validity: LSB-first bitmap over the batch
+// rows, NULL = all present; under writer setting 0 the caller has already
+// refused a batch with a null, and the file is the REQUIRED one.
+static hx_status write_batch(hx_handle* h, const uint64_t* series,
+                             const int64_t* ts, const double* value,
+                             const uint8_t* validity, int64_t n,
+                             int32_t enable_check, uint64_t* out_seq) {
     // ColumnarStorage::write (storage.rs:76-89, :307-333): sort the batch by
     // primary key (sort_batch, storage.rs:244-256 — GPU radix sort when a
     // device is visible, the reference's CPU SortExec otherwise is NOT
@@ -2400,9 +2575,15 @@ extern "C" hx_status hx_write(hx_handle* h, const uint64_t* series,
     std::vector<uint64_t> s2(n);
     std::vector<int64_t> t2(n);
     std::vector<double> v2(n);
+    // nullable writer: validity follows its row through the sort, and the
+    // values are packed per row group by the sort permutation (kernel 1d on
+    // the device path, its host twin here)
+    const bool nullable = h->nullable_values != 0;
+    PackedValues pv;
     bool sorted_on_gpu = false;
     if (n >= (1 << 16) && hip_device_count() > 0) {
-        sorted_on_gpu = gpu_sort_batch(series, ts, value, n, s2, t2, v2);
+        sorted_on_gpu = gpu_sort_batch(series, ts, value, n, s2, t2, v2,
+                                       validity, nullable ? &pv : nullptr);
     }
     if (!sorted_on_gpu) {
         std::vector<uint32_t> order(n);
@@ -2418,20 +2599,257 @@ extern "C" hx_status hx_write(hx_handle* h, const uint64_t* series,
             t2[i] = ts[order[i]];
             v2[i] = value[order[i]];
         }
+        if (nullable) {
+            pv.resize(n, kRowGroup);
+            hx::pack_optional_host((const uint64_t*)value, validity,
+                                   order.data(), (uint64_t)n, (uint64_t)n,
+                                   (uint64_t)kRowGroup, pv.packed.data(),
+                                   pv.bitmap.data(), pv.n_valid.data());
+        }
     }
     uint64_t max_seq = 0;
     for (const auto& s : h->ssts) max_seq = std::max(max_seq, s.seq);
     const uint64_t new_seq = max_seq + 1;
     std::string out_path = h->store + "/data/" + std::to_string(new_seq) +
                            ".sst";
-    std::string werr = hx::write_metric_sst(out_path, s2.data(), t2.data(),
-                                            v2.data(), new_seq, n, 8192);
+    std::string werr =
+        nullable ? hx::write_metric_sst_nullable(out_path, s2.data(),
+                                                 t2.data(), pv.view(), nullptr,
+                                                 new_seq, n, kRowGroup)
+                 : hx::write_metric_sst(out_path, s2.data(), t2.data(),
+                                        v2.data(), new_seq, n, kRowGroup);
     if (!werr.empty()) return fail(HX_ERR_IO, werr);
     CatSst fresh;
     hx_status st = read_file_meta(out_path, new_seq, fresh);
     if (st != HX_OK) return st;
     h->ssts.push_back(std::move(fresh));
     *out_seq = new_seq;
+    return HX_OK;
+}
+
+extern "C" hx_status hx_write(hx_handle* h, const uint64_t* series,
+                              const int64_t* ts, const double* value,
+                              int64_t n, int32_t enable_check,
+                              uint64_t* out_seq) {
+    return write_batch(h, series, ts, value, nullptr, n, enable_check,
+                       out_seq);
+}
+
+extern "C" hx_status hx_write_nullable(hx_handle* h, const uint64_t* series,
+                                       const int64_t* ts, const double* value,
+                                       const uint8_t* validity, int64_t n,
+                                       int32_t enable_check,
+                                       uint64_t* out_seq) {
+    if (h && out_seq && n > 0 && validity && !h->nullable_values) {
+        if (count_nulls(validity, n) > 0) {
+            *out_seq = 0;
+            return fail(HX_ERR_UNSUPPORTED,
+                        "batch holds null values and the handle writes "
+                        "REQUIRED columns (hx_set_nullable_values)");
+        }
+        validity = nullptr;   // all present: the file hx_write writes
+    }
+    return write_batch(h, series, ts, value, validity, n, enable_check,
+                       out_seq);
+}
+
+// The shared body of hx_compact and hx_compact_files, from the prepared plan
+// to the catalog update: filter + dedup into a row stream, two stable sort
+// passes (ts, then series), gather by the final permutation, one D2H, the
+// native writer, then add-before-delete. keep_seq: the rows keep their own
+// __seq__ (hx_compact_files); otherwise the file carries the fresh id.
+// Writer setting 1 (hx_set_nullable_values): null values survive. The scan
+// emits one validity word per row when the plan staged a null; series, ts
+// (and seq) are gathered as before and kernel 1d packs the values per output
+// row group by the same permutation, so the host receives packed values,
+// bitmaps and counts, never the 8-byte validity words.
+static hx_status compact_rows(hx_handle* h, hx_prepared* P,
+                              const std::vector<char>& in_set,
+                              uint64_t max_seq, bool keep_seq,
+                              uint64_t* out_new_seq) {
+    DevPlan& plan = P->plans[0];
+    const bool nullable = h->nullable_values != 0;
+    // the REQUIRED writer cannot keep a null: dropping it would be data
+    // loss. Refused before anything is written or unlinked.
+    if (plan.has_nulls && !nullable)
+        return fail(HX_ERR_UNSUPPORTED,
+                    "compaction inputs hold null values (the native writer "
+                    "writes REQUIRED columns)");
+    HIP_TRY(hipSetDevice(plan.device));
+    hipStream_t s = plan.stream;
+    hx_status st = ensure_decoded(plan, s);
+    if (st != HX_OK) return st;
+
+    const uint64_t cap = (uint64_t)plan.rows_scanned;
+    if (cap == 0) return HX_OK;
+    if (cap > 0xFFFFFFFFull)
+        return fail(HX_ERR_UNSUPPORTED,
+                    "row streams above 2^32 rows per call: split the range");
+    const bool nulls = plan.has_nulls;
+    const uint32_t n_cols = keep_seq ? 4 : 3;
+    size_t need = cap * 8 * (n_cols + 2 + (nulls ? 1 : 0)) + cap * 4 * 3 + 64;
+    st = ensure_dev(&plan.d_scratch, &plan.scratch_cap, need);
+    if (st != HX_OK) return st;
+    uint8_t* base = (uint8_t*)plan.d_scratch;
+    auto carve8 = [&](size_t count) {
+        uint8_t* p = base;
+        base += (count * 8 + 7) & ~size_t(7);
+        return p;
+    };
+    uint64_t* d_series = (uint64_t*)carve8(cap);
+    long long* d_ts = (long long*)carve8(cap);
+    double* d_val = (double*)carve8(cap);
+    uint64_t* d_seq = keep_seq ? (uint64_t*)carve8(cap) : nullptr;
+    uint64_t* d_keys = (uint64_t*)carve8(cap);
+    uint64_t* d_keys_out = (uint64_t*)carve8(cap);
+    unsigned long long* d_cursor = (unsigned long long*)carve8(1);
+    uint32_t* perm_a = (uint32_t*)base; base += cap * 4;
+    uint32_t* perm_b = (uint32_t*)base; base += cap * 4;
+    uint32_t* perm_c = (uint32_t*)base; base += cap * 4;
+    // one 0/1 word per surviving row (behind the perms, 8-aligned)
+    base = (uint8_t*)(((uintptr_t)base + 7) & ~uintptr_t(7));
+    uint64_t* d_valid = nulls ? (uint64_t*)carve8(cap) : nullptr;
+
+    HIP_TRY(hipMemsetAsync(d_cursor, 0, 8, s));
+    hx::AggParams A = base_params(P, plan);
+    HIP_TRY(hx::launch_scan_rows(s, A, 0, A.n_rgs, d_series, d_ts, d_val,
+                                 d_cursor, cap, d_seq, 0, d_valid));
+    unsigned long long n64 = 0;
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpy(&n64, d_cursor, 8, hipMemcpyDeviceToHost));
+    if (n64 > cap) return fail(HX_ERR_HIP, "compact row buffer overflow");
+    const uint32_t n = (uint32_t)n64;
+    if (n == 0) return HX_OK;
+
+    HIP_TRY(hx::launch_iota(s, perm_a, n));
+    HIP_TRY(hx::launch_gather_u64(s, (const unsigned long long*)d_ts, perm_a,
+                                  (unsigned long long*)d_keys, n));
+    HIP_TRY(hx::launch_xor_sign(s, (unsigned long long*)d_keys, n));
+    HIP_TRY(hx::sort_pairs_u64(s, d_keys, d_keys_out, perm_a, perm_b, n,
+                               &plan.d_sort_temp, &plan.sort_temp_cap));
+    HIP_TRY(hx::launch_gather_u64(s, (const unsigned long long*)d_series,
+                                  perm_b, (unsigned long long*)d_keys, n));
+    HIP_TRY(hx::sort_pairs_u64(s, d_keys, d_keys_out, perm_b, perm_c, n,
+                               &plan.d_sort_temp, &plan.sort_temp_cap));
+    const uint32_t* perm = perm_c;
+
+    // gather destination, one D2H: series, ts, value [, seq]; the nullable
+    // form has the packed values in the value slot and the bitmaps, counts
+    // and the error count behind the columns
+    const size_t n_groups = (size_t(n) + kRowGroup - 1) / kRowGroup;
+    const size_t bm_words = n_groups * size_t(kRowGroup / 64);
+    const size_t nv_words = (n_groups + 1) / 2;   // u32 counts, in 8-byte units
+    const size_t words = size_t(n_cols) * n +
+                         (nullable ? bm_words + nv_words + 1 : 0);
+    std::vector<uint64_t> host(words);
+    unsigned long long* d_dst = nullptr;
+    HIP_TRY(hipMalloc((void**)&d_dst, words * 8));
+    std::unique_ptr<void, void (*)(void*)> dst_guard(
+        d_dst, [](void* q) { (void)hipFree(q); });
+    // HX_DEBUG: HIP-event times of the final gather and of kernel 1d
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    const bool timed = getenv("HX_DEBUG") != nullptr;
+    struct EvGuard {
+        hipEvent_t* e;
+        ~EvGuard() {
+            for (int i = 0; i < 3; i++)
+                if (e[i]) (void)hipEventDestroy(e[i]);
+        }
+    } ev_guard{ev};
+    if (timed) {
+        for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
+        HIP_TRY(hipEventRecord(ev[0], s));
+    }
+    if (nullable) {
+        // slots 0 and 1 by the gather, slot 2 by the pack kernel, slot 3
+        // (seq) by a gather of its own
+        unsigned long long* d_bm = d_dst + size_t(n_cols) * n;
+        unsigned long long* d_nv = d_bm + bm_words;
+        unsigned long long* d_err = d_nv + nv_words;
+        HIP_TRY(hipMemsetAsync(d_err, 0, 8, s));
+        const unsigned long long* srcs[2] = {
+            (const unsigned long long*)d_series,
+            (const unsigned long long*)d_ts};
+        HIP_TRY(hx::launch_gather_multi(s, srcs, 2, perm, d_dst, n));
+        if (keep_seq)
+            HIP_TRY(hx::launch_gather_u64(
+                s, (const unsigned long long*)d_seq, perm,
+                d_dst + 3 * size_t(n), n));
+        if (timed) HIP_TRY(hipEventRecord(ev[1], s));
+        HIP_TRY(hx::launch_pack_optional(
+            s, (const unsigned long long*)d_val, d_valid, false, perm, n, n,
+            (uint32_t)kRowGroup, d_dst + 2 * size_t(n), (uint64_t*)d_bm,
+            (uint32_t*)d_nv, d_err));
+    } else {
+        const unsigned long long* srcs[4] = {
+            (const unsigned long long*)d_series,
+            (const unsigned long long*)d_ts,
+            (const unsigned long long*)d_val,
+            (const unsigned long long*)d_seq};
+        HIP_TRY(hx::launch_gather_multi(s, srcs, n_cols, perm, d_dst, n));
+        if (timed) HIP_TRY(hipEventRecord(ev[1], s));
+    }
+    if (timed) HIP_TRY(hipEventRecord(ev[2], s));
+    HIP_TRY(hipMemcpyAsync(host.data(), d_dst, words * 8,
+                           hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    dst_guard.reset();
+    if (timed) {
+        float gather_ms = 0, pack_ms = 0;
+        HIP_TRY(hipEventElapsedTime(&gather_ms, ev[0], ev[1]));
+        HIP_TRY(hipEventElapsedTime(&pack_ms, ev[1], ev[2]));
+        fprintf(stderr,
+                "[hx] compact rows=%u cols_gathered=%u nullable=%d nulls=%d "
+                "gather_ms=%.4f pack_ms=%.4f d2h_bytes=%zu\n",
+                n, nullable ? n_cols - 1 : n_cols, int(nullable), int(nulls),
+                gather_ms, pack_ms, words * 8);
+    }
+
+    const uint64_t new_seq = max_seq + 1;  // fresh file id (sst.rs:39-46)
+    std::string out_path = h->store + "/data/" + std::to_string(new_seq) +
+                           ".sst";
+    const uint64_t* h_series = host.data();
+    const int64_t* h_ts = (const int64_t*)(host.data() + n);
+    const uint64_t* h_val = host.data() + 2 * size_t(n);
+    const uint64_t* h_seq = keep_seq ? host.data() + 3 * size_t(n) : nullptr;
+    std::string werr;
+    if (nullable) {
+        const uint64_t* h_bm = host.data() + size_t(n_cols) * n;
+        if (h_bm[bm_words + nv_words] != 0)
+            return fail(HX_ERR_HIP, "compact: sort permutation out of range");
+        hx::NullableValues nv{h_val, h_bm,
+                              (const uint32_t*)(h_bm + bm_words)};
+        werr = hx::write_metric_sst_nullable(out_path, h_series, h_ts, nv,
+                                             h_seq, new_seq, n, kRowGroup);
+    } else if (keep_seq) {
+        werr = hx::write_metric_sst_seqs(out_path, h_series, h_ts,
+                                         (const double*)h_val, h_seq, n,
+                                         kRowGroup);
+    } else {
+        werr = hx::write_metric_sst(out_path, h_series, h_ts,
+                                    (const double*)h_val, new_seq, n,
+                                    kRowGroup);
+    }
+    if (!werr.empty()) return fail(HX_ERR_IO, werr);
+
+    // catalog update: add new file, drop + unlink inputs (add-before-delete,
+    // executor.rs:206-220)
+    CatSst fresh;
+    st = read_file_meta(out_path, new_seq, fresh);
+    if (st != HX_OK) return st;
+    std::vector<CatSst> kept;
+    for (size_t i = 0; i < h->ssts.size(); i++) {
+        if (in_set[i]) {
+            unlink(h->ssts[i].path.c_str());  // best-effort, like the reference
+            continue;
+        }
+        kept.push_back(std::move(h->ssts[i]));
+    }
+    kept.push_back(std::move(fresh));
+    std::sort(kept.begin(), kept.end(),
+              [](const CatSst& a, const CatSst& b) { return a.seq < b.seq; });
+    h->ssts = std::move(kept);
+    *out_new_seq = new_seq;
     return HX_OK;
 }
 
@@ -2490,104 +2908,7 @@ extern "C" hx_status hx_compact(hx_handle* h, hx_time_range range,
     if (st != HX_OK) return st;
     std::unique_ptr<hx_prepared, void (*)(hx_prepared*)> guard(
         P, hx_prepared_free);
-    DevPlan& plan = P->plans[0];
-    // the native writer writes REQUIRED columns: dropping the nulls would be
-    // data loss. Refused before anything is written or unlinked.
-    if (plan.has_nulls)
-        return fail(HX_ERR_UNSUPPORTED,
-                    "compaction inputs hold null values (the native writer "
-                    "writes REQUIRED columns)");
-    HIP_TRY(hipSetDevice(plan.device));
-    hipStream_t s = plan.stream;
-    st = ensure_decoded(plan, s);
-    if (st != HX_OK) return st;
-
-    const uint64_t cap = (uint64_t)plan.rows_scanned;
-    if (cap == 0) return HX_OK;
-    if (cap > 0xFFFFFFFFull)
-        return fail(HX_ERR_UNSUPPORTED,
-                    "row streams above 2^32 rows per call: split the range");
-    size_t need = cap * 8 * 5 + cap * 4 * 3 + 64;
-    st = ensure_dev(&plan.d_scratch, &plan.scratch_cap, need);
-    if (st != HX_OK) return st;
-    uint8_t* base = (uint8_t*)plan.d_scratch;
-    auto carve8 = [&](size_t count) {
-        uint8_t* p = base;
-        base += (count * 8 + 7) & ~size_t(7);
-        return p;
-    };
-    uint64_t* d_series = (uint64_t*)carve8(cap);
-    long long* d_ts = (long long*)carve8(cap);
-    double* d_val = (double*)carve8(cap);
-    uint64_t* d_keys = (uint64_t*)carve8(cap);
-    uint64_t* d_keys_out = (uint64_t*)carve8(cap);
-    unsigned long long* d_cursor = (unsigned long long*)carve8(1);
-    uint32_t* perm_a = (uint32_t*)base; base += cap * 4;
-    uint32_t* perm_b = (uint32_t*)base; base += cap * 4;
-    uint32_t* perm_c = (uint32_t*)base; base += cap * 4;
-
-    HIP_TRY(hipMemsetAsync(d_cursor, 0, 8, s));
-    hx::AggParams A = base_params(P, plan);
-    HIP_TRY(hx::launch_scan_rows(s, A, 0, A.n_rgs, d_series, d_ts, d_val,
-                                 d_cursor, cap));
-    unsigned long long n64 = 0;
-    HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(hipMemcpy(&n64, d_cursor, 8, hipMemcpyDeviceToHost));
-    if (n64 > cap) return fail(HX_ERR_HIP, "compact row buffer overflow");
-    const uint32_t n = (uint32_t)n64;
-    if (n == 0) return HX_OK;
-
-    HIP_TRY(hx::launch_iota(s, perm_a, n));
-    HIP_TRY(hx::launch_gather_u64(s, (const unsigned long long*)d_ts, perm_a,
-                                  (unsigned long long*)d_keys, n));
-    HIP_TRY(hx::launch_xor_sign(s, (unsigned long long*)d_keys, n));
-    HIP_TRY(hx::sort_pairs_u64(s, d_keys, d_keys_out, perm_a, perm_b, n,
-                               &plan.d_sort_temp, &plan.sort_temp_cap));
-    HIP_TRY(hx::launch_gather_u64(s, (const unsigned long long*)d_series,
-                                  perm_b, (unsigned long long*)d_keys, n));
-    HIP_TRY(hx::sort_pairs_u64(s, d_keys, d_keys_out, perm_b, perm_c, n,
-                               &plan.d_sort_temp, &plan.sort_temp_cap));
-    const uint32_t* perm = perm_c;
-
-    std::vector<uint64_t> host(3 * size_t(n));
-    unsigned long long* d_dst = nullptr;
-    HIP_TRY(hipMalloc((void**)&d_dst, 3 * size_t(n) * 8));
-    const unsigned long long* srcs[3] = {
-        (const unsigned long long*)d_series, (const unsigned long long*)d_ts,
-        (const unsigned long long*)d_val};
-    HIP_TRY(hx::launch_gather_multi(s, srcs, 3, perm, d_dst, n));
-    HIP_TRY(hipMemcpyAsync(host.data(), d_dst, 3 * size_t(n) * 8,
-                           hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    hipFree(d_dst);
-
-    const uint64_t new_seq = max_seq + 1;  // fresh file id (sst.rs:39-46)
-    std::string out_path = h->store + "/data/" + std::to_string(new_seq) +
-                           ".sst";
-    std::string werr = hx::write_metric_sst(
-        out_path, host.data(), (const int64_t*)(host.data() + n),
-        (const double*)(host.data() + 2 * size_t(n)), new_seq, n, 8192);
-    if (!werr.empty()) return fail(HX_ERR_IO, werr);
-
-    // catalog update: add new file, drop + unlink inputs (add-before-delete,
-    // executor.rs:206-220)
-    CatSst fresh;
-    st = read_file_meta(out_path, new_seq, fresh);
-    if (st != HX_OK) return st;
-    std::vector<CatSst> kept;
-    for (size_t i = 0; i < h->ssts.size(); i++) {
-        if (in_set[i]) {
-            unlink(h->ssts[i].path.c_str());  // best-effort, like the reference
-            continue;
-        }
-        kept.push_back(std::move(h->ssts[i]));
-    }
-    kept.push_back(std::move(fresh));
-    std::sort(kept.begin(), kept.end(),
-              [](const CatSst& a, const CatSst& b) { return a.seq < b.seq; });
-    h->ssts = std::move(kept);
-    *out_new_seq = new_seq;
-    return HX_OK;
+    return compact_rows(h, P, in_set, max_seq, false, out_new_seq);
 }
 
 extern "C" hx_status hx_compact_files(hx_handle* h,
@@ -2637,104 +2958,7 @@ extern "C" hx_status hx_compact_files(hx_handle* h,
     if (st != HX_OK) return st;
     std::unique_ptr<hx_prepared, void (*)(hx_prepared*)> guard(
         P, hx_prepared_free);
-    DevPlan& plan = P->plans[0];
-    // the native writer writes REQUIRED columns: dropping the nulls would be
-    // data loss. Refused before anything is written or unlinked.
-    if (plan.has_nulls)
-        return fail(HX_ERR_UNSUPPORTED,
-                    "compaction inputs hold null values (the native writer "
-                    "writes REQUIRED columns)");
-    HIP_TRY(hipSetDevice(plan.device));
-    hipStream_t s = plan.stream;
-    st = ensure_decoded(plan, s);
-    if (st != HX_OK) return st;
-
-    const uint64_t cap = (uint64_t)plan.rows_scanned;
-    if (cap == 0) return HX_OK;
-    if (cap > 0xFFFFFFFFull)
-        return fail(HX_ERR_UNSUPPORTED,
-                    "row streams above 2^32 rows per call: split the range");
-    size_t need = cap * 8 * 6 + cap * 4 * 3 + 64;
-    st = ensure_dev(&plan.d_scratch, &plan.scratch_cap, need);
-    if (st != HX_OK) return st;
-    uint8_t* base = (uint8_t*)plan.d_scratch;
-    auto carve8 = [&](size_t count) {
-        uint8_t* p = base;
-        base += (count * 8 + 7) & ~size_t(7);
-        return p;
-    };
-    uint64_t* d_series = (uint64_t*)carve8(cap);
-    long long* d_ts = (long long*)carve8(cap);
-    double* d_val = (double*)carve8(cap);
-    uint64_t* d_seq = (uint64_t*)carve8(cap);
-    uint64_t* d_keys = (uint64_t*)carve8(cap);
-    uint64_t* d_keys_out = (uint64_t*)carve8(cap);
-    unsigned long long* d_cursor = (unsigned long long*)carve8(1);
-    uint32_t* perm_a = (uint32_t*)base; base += cap * 4;
-    uint32_t* perm_b = (uint32_t*)base; base += cap * 4;
-    uint32_t* perm_c = (uint32_t*)base; base += cap * 4;
-
-    HIP_TRY(hipMemsetAsync(d_cursor, 0, 8, s));
-    hx::AggParams A = base_params(P, plan);
-    HIP_TRY(hx::launch_scan_rows(s, A, 0, A.n_rgs, d_series, d_ts, d_val,
-                                 d_cursor, cap, d_seq));
-    unsigned long long n64 = 0;
-    HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(hipMemcpy(&n64, d_cursor, 8, hipMemcpyDeviceToHost));
-    if (n64 > cap) return fail(HX_ERR_HIP, "compact row buffer overflow");
-    const uint32_t n = (uint32_t)n64;
-    if (n == 0) return HX_OK;
-
-    HIP_TRY(hx::launch_iota(s, perm_a, n));
-    HIP_TRY(hx::launch_gather_u64(s, (const unsigned long long*)d_ts, perm_a,
-                                  (unsigned long long*)d_keys, n));
-    HIP_TRY(hx::launch_xor_sign(s, (unsigned long long*)d_keys, n));
-    HIP_TRY(hx::sort_pairs_u64(s, d_keys, d_keys_out, perm_a, perm_b, n,
-                               &plan.d_sort_temp, &plan.sort_temp_cap));
-    HIP_TRY(hx::launch_gather_u64(s, (const unsigned long long*)d_series,
-                                  perm_b, (unsigned long long*)d_keys, n));
-    HIP_TRY(hx::sort_pairs_u64(s, d_keys, d_keys_out, perm_b, perm_c, n,
-                               &plan.d_sort_temp, &plan.sort_temp_cap));
-    const uint32_t* perm = perm_c;
-
-    std::vector<uint64_t> host(4 * size_t(n));
-    unsigned long long* d_dst = nullptr;
-    HIP_TRY(hipMalloc((void**)&d_dst, 4 * size_t(n) * 8));
-    const unsigned long long* srcs[4] = {
-        (const unsigned long long*)d_series, (const unsigned long long*)d_ts,
-        (const unsigned long long*)d_val, (const unsigned long long*)d_seq};
-    HIP_TRY(hx::launch_gather_multi(s, srcs, 4, perm, d_dst, n));
-    HIP_TRY(hipMemcpyAsync(host.data(), d_dst, 4 * size_t(n) * 8,
-                           hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    (void)hipFree(d_dst);
-
-    const uint64_t new_seq = max_seq + 1;  // fresh file id (sst.rs:39-46)
-    std::string out_path = h->store + "/data/" + std::to_string(new_seq) +
-                           ".sst";
-    std::string werr = hx::write_metric_sst_seqs(
-        out_path, host.data(), (const int64_t*)(host.data() + n),
-        (const double*)(host.data() + 2 * size_t(n)),
-        host.data() + 3 * size_t(n), n, 8192);
-    if (!werr.empty()) return fail(HX_ERR_IO, werr);
-
-    CatSst fresh;
-    st = read_file_meta(out_path, new_seq, fresh);
-    if (st != HX_OK) return st;
-    std::vector<CatSst> kept;
-    for (size_t i = 0; i < h->ssts.size(); i++) {
-        if (in_set[i]) {
-            unlink(h->ssts[i].path.c_str());
-            continue;
-        }
-        kept.push_back(std::move(h->ssts[i]));
-    }
-    kept.push_back(std::move(fresh));
-    std::sort(kept.begin(), kept.end(),
-              [](const CatSst& a, const CatSst& b) { return a.seq < b.seq; });
-    h->ssts = std::move(kept);
-    *out_new_seq = new_seq;
-    return HX_OK;
+    return compact_rows(h, P, in_set, max_seq, true, out_new_seq);
 }
 
 // introspection used by CPU tests (no GPU needed): per-SST catalog entries

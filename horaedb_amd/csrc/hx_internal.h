@@ -39,3 +39,20 @@ extern "C" hx_status hx_debug_page_levels(
     const char* path, int32_t row_group, const char* column,
     uint64_t* bitmap_out, uint64_t cap_words, int64_t* n_rows,
     int64_t* n_valid, int32_t* level_bytes);
+
+// Test hook (exported, not part of the public C-ABI): run the production
+// launch of kernel 1d (hx::launch_pack_optional, hx_kernels.h) once over
+// caller-built arrays on the current device. values: n_src 8-byte values.
+// Validity over SOURCE rows, at most one of valid_words (one 0/1 word per
+// row) and valid_bits (LSB-first bitmap, (n_src + 7) / 8 bytes); both NULL =
+// all present. perm: n entries or NULL (identity). Outputs, row-group-major:
+// packed_out n slots (row group g's present values from g * row_group; slots
+// past its count are unspecified), bitmap_out ceil(n / row_group) *
+// (row_group / 64) words, n_valid_out one count per row group. *n_errors
+// receives the number of perm entries >= n_src (their rows come back null).
+// Every device buffer is exactly as large as stated here.
+extern "C" hx_status hx_debug_pack_optional(
+    const uint64_t* values, const uint64_t* valid_words,
+    const uint8_t* valid_bits, const uint32_t* perm, uint32_t n_src,
+    uint32_t n, uint32_t row_group, uint64_t* packed_out,
+    uint64_t* bitmap_out, uint32_t* n_valid_out, uint64_t* n_errors);

@@ -32,6 +32,22 @@ hipError_t launch_expand_optional(hipStream_t s, const uint8_t* blob,
                                   uint8_t* dec, const ExpandPageDesc* pages,
                                   uint32_t n_pages,
                                   unsigned long long* err_flag);
+// Kernel 1d, one workgroup per output row group of row_group rows (a multiple
+// of 64, else hipErrorInvalidValue): output row i of n is source row perm[i]
+// (i when perm is null) of n_src. valid_src: one 0/1 u64 per source row, or
+// (valid_bits) an LSB-first bitmap of ceil(n_src / 8) bytes; null = all
+// present. Writes, row-group-major: bitmap_out[g * (row_group / 64) ...]
+// (every word of every row group, n_groups * row_group / 64 in all),
+// packed_out[g * row_group ...] (n slots in all), n_valid[g]. A perm entry
+// >= n_src is counted in err_flag and its row written as null.
+hipError_t launch_pack_optional(hipStream_t s,
+                                const unsigned long long* val_src,
+                                const void* valid_src, bool valid_bits,
+                                const uint32_t* perm, uint32_t n_src,
+                                uint32_t n, uint32_t row_group,
+                                unsigned long long* packed_out,
+                                uint64_t* bitmap_out, uint32_t* n_valid,
+                                unsigned long long* err_flag);
 hipError_t launch_copy_u64(hipStream_t s, const uint8_t* blob, uint8_t* dec,
                            const CopyDesc* descs, uint32_t n_descs);
 // nulls: the plan staged a validity bitmap — launch the null-aware instance

@@ -1743,6 +1743,106 @@ k_expand_optional(const uint8_t* blob, const uint8_t* dec_in, uint8_t* dec,
 }
 
 // ---------------------------------------------------------------------------
+// Kernel 1d: the inverse of kernel 1c, fused with the last gather
+// of the row-stream pipeline. One workgroup per OUTPUT row group g of R rows
+// (R a multiple of 64): output row i = g * R + r is source row perm[i] (i when
+// perm is null). A wave64 ballot of "row present" is one bitmap word; the
+// words' popcounts go through the same LDS scan as kernel 1c (tiles of 128
+// words, rank carried from tile to tile), and a present row stores its value
+// at packed_out[g * R + rank]. The tile's words stay in LDS, so the validity
+// source is gathered once per row; perm is read a second time (coalesced) for
+// the value gather. A block writes its own row group's slots only: plain
+// stores, no atomics but the error counter. Validity source: one 0/1 word
+// per source row (k_scan_rows' out_valid), or an LSB-first bitmap read by
+// bytes (nothing past ceil(n_src / 8) bytes is touched); null = all present.
+// A perm entry >= n_src counts one error and its row is written as null.
+// All R / 64 bitmap words of a row group are written, the ones past a short
+// last row group as zero.
+// ---------------------------------------------------------------------------
+template <bool BITS>
+__global__ void __launch_bounds__(256)
+k_pack_optional(const unsigned long long* __restrict__ val_src,
+                const void* __restrict__ valid_src,
+                const uint32_t* __restrict__ perm, uint32_t n_src, uint32_t n,
+                uint32_t R, unsigned long long* __restrict__ packed_out,
+                uint64_t* __restrict__ bitmap_out,
+                uint32_t* __restrict__ n_valid,
+                unsigned long long* err_flag) {
+    __shared__ uint64_t words[EXPAND_TILE_WORDS];
+    __shared__ uint32_t wrank[EXPAND_TILE_WORDS];   // inclusive, within tile
+    __shared__ uint32_t tile_total;
+    const uint32_t wpg = R >> 6;
+    const uint32_t n_groups = (uint32_t)(((uint64_t)n + R - 1) / R);
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (uint32_t g = blockIdx.x; g < n_groups; g += gridDim.x) {
+        const uint64_t row0 = (uint64_t)g * R;
+        const uint32_t rows =
+            (uint64_t)n - row0 < R ? (uint32_t)(n - row0) : R;
+        uint32_t carry = 0;       // present rows before this tile
+        for (uint32_t w0 = 0; w0 < wpg; w0 += EXPAND_TILE_WORDS) {
+            const uint32_t tw = wpg - w0 < EXPAND_TILE_WORDS
+                                    ? wpg - w0 : EXPAND_TILE_WORDS;
+            __syncthreads();   // previous tile's words/wrank fully consumed
+            for (uint32_t wi = wave; wi < EXPAND_TILE_WORDS; wi += 4) {
+                bool present = false;
+                const uint32_t r = ((w0 + wi) << 6) + lane;
+                if (wi < tw && r < rows) {
+                    const uint32_t p =
+                        perm ? perm[row0 + r] : (uint32_t)(row0 + r);
+                    if (p >= n_src)
+                        atomicAdd(err_flag, 1ull);
+                    else if (!valid_src)
+                        present = true;
+                    else if (BITS)
+                        present = (((const uint8_t*)valid_src)[p >> 3] >>
+                                   (p & 7u)) & 1u;
+                    else
+                        present = ((const uint64_t*)valid_src)[p] != 0;
+                }
+                const uint64_t m = __ballot(present);
+                if (lane == 0) {
+                    words[wi] = m;
+                    wrank[wi] = (uint32_t)__popcll(m);
+                    if (wi < tw) bitmap_out[(uint64_t)g * wpg + w0 + wi] = m;
+                }
+            }
+            __syncthreads();
+            // inclusive Hillis-Steele scan over the 128 counts
+            for (uint32_t d = 1; d < EXPAND_TILE_WORDS; d <<= 1) {
+                uint32_t add = 0;
+                if (threadIdx.x < EXPAND_TILE_WORDS && threadIdx.x >= d)
+                    add = wrank[threadIdx.x - d];
+                __syncthreads();
+                if (threadIdx.x < EXPAND_TILE_WORDS) wrank[threadIdx.x] += add;
+                __syncthreads();
+            }
+            if (threadIdx.x == 0) tile_total = wrank[EXPAND_TILE_WORDS - 1];
+            __syncthreads();
+            const uint32_t r_end = (w0 + tw) << 6 < rows ? (w0 + tw) << 6
+                                                         : rows;
+            for (uint32_t r = (w0 << 6) + threadIdx.x; r < r_end;
+                 r += blockDim.x) {
+                const uint32_t wi = (r >> 6) - w0;
+                const uint64_t wv = words[wi];
+                if ((wv >> (r & 63u)) & 1ull) {
+                    const uint32_t before =
+                        (uint32_t)__popcll(wv & ((1ull << (r & 63u)) - 1ull));
+                    // exclusive rank of the word = inclusive - its own count
+                    const uint32_t k = carry + wrank[wi] -
+                                       (uint32_t)__popcll(wv) + before;
+                    // a set bit means p < n_src was checked above
+                    const uint32_t p =
+                        perm ? perm[row0 + r] : (uint32_t)(row0 + r);
+                    packed_out[row0 + k] = val_src[p];
+                }
+            }
+            carry += tile_total;
+        }
+        if (threadIdx.x == 0) n_valid[g] = carry;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Snappy raw-block decompression (the reference's default page codec,
 // config.rs:120-133). One WAVE per page: the tag stream is inherently
 // sequential, so every lane parses the (wave-uniform) element headers and
@@ -2716,6 +2816,29 @@ hipError_t launch_expand_optional(hipStream_t s, const uint8_t* blob,
     uint32_t grid = n_pages > 65535 ? 65535 : n_pages;
     hipLaunchKernelGGL(k_expand_optional, dim3(grid), dim3(256), 0, s,
                        blob, dec, dec, pages, n_pages, err_flag);
+    return hipGetLastError();
+}
+
+hipError_t launch_pack_optional(hipStream_t s,
+                                const unsigned long long* val_src,
+                                const void* valid_src, bool valid_bits,
+                                const uint32_t* perm, uint32_t n_src,
+                                uint32_t n, uint32_t row_group,
+                                unsigned long long* packed_out,
+                                uint64_t* bitmap_out, uint32_t* n_valid,
+                                unsigned long long* err_flag) {
+    if (row_group == 0 || (row_group & 63u)) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    const uint64_t n_groups = ((uint64_t)n + row_group - 1) / row_group;
+    const uint32_t grid = n_groups > 65535 ? 65535u : (uint32_t)n_groups;
+    if (valid_bits)
+        hipLaunchKernelGGL(k_pack_optional<true>, dim3(grid), dim3(256), 0, s,
+                           val_src, valid_src, perm, n_src, n, row_group,
+                           packed_out, bitmap_out, n_valid, err_flag);
+    else
+        hipLaunchKernelGGL(k_pack_optional<false>, dim3(grid), dim3(256), 0,
+                           s, val_src, valid_src, perm, n_src, n, row_group,
+                           packed_out, bitmap_out, n_valid, err_flag);
     return hipGetLastError();
 }
 

@@ -2,6 +2,7 @@
 // (field ids per parquet-format/src/main/thrift/parquet.thrift; the inverse
 // of thrift_compact.h's reader).
 #include "parquet_writer.h"
+#include "def_levels.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -73,10 +74,10 @@ const ColSpec kCols[5] = {
     {"__seq__", 2, 14},   {"__reserved__", 2, 14},
 };  // 14 = ConvertedType::UINT_64
 
-void schema_element(TW& w, const ColSpec& c) {
+void schema_element(TW& w, const ColSpec& c, bool optional) {
     int16_t last = 0;
     w.i32(last, 1, c.physical);            // type
-    w.i32(last, 3, 0);                     // repetition REQUIRED
+    w.i32(last, 3, optional ? 1 : 0);      // repetition REQUIRED / OPTIONAL
     w.str(last, 4, c.name);                // name
     if (c.converted >= 0) w.i32(last, 6, c.converted);
     w.stop();
@@ -95,7 +96,21 @@ struct ChunkMeta {
     int64_t num_values;
     std::string mn, mx;
     bool has_stats = true;
+    // OPTIONAL chunk: RLE joins the encodings and the statistics always carry
+    // null_count, with bounds only when has_stats
+    bool optional = false;
+    int64_t null_count = 0;
 };
+
+void statistics_optional(TW& w, const ChunkMeta& m) {
+    int16_t last = 0;
+    w.i64f(last, 3, m.null_count);
+    if (m.has_stats) {
+        w.binary(last, 5, m.mx.data(), m.mx.size());
+        w.binary(last, 6, m.mn.data(), m.mn.size());
+    }
+    w.stop();
+}
 
 void column_chunk(TW& w, const char* name, int32_t physical,
                   const ChunkMeta& m) {
@@ -106,8 +121,14 @@ void column_chunk(TW& w, const char* name, int32_t physical,
     {
         int16_t l2 = 0;
         w.i32(l2, 1, physical);                        // type
-        w.list_header(l2, 2, 5, 1);                    // encodings: [PLAIN]
-        w.zigzag(0);
+        if (m.optional) {
+            w.list_header(l2, 2, 5, 2);                // encodings: [PLAIN, RLE]
+            w.zigzag(0);
+            w.zigzag(3);
+        } else {
+            w.list_header(l2, 2, 5, 1);                // encodings: [PLAIN]
+            w.zigzag(0);
+        }
         w.list_header(l2, 3, 8, 1);                    // path_in_schema
         w.varint(strlen(name));
         w.buf.insert(w.buf.end(), (const uint8_t*)name,
@@ -117,7 +138,10 @@ void column_chunk(TW& w, const char* name, int32_t physical,
         w.i64f(l2, 6, m.total_size);                   // uncompressed
         w.i64f(l2, 7, m.total_size);                   // compressed
         w.i64f(l2, 9, m.data_page_offset);
-        if (m.has_stats) {
+        if (m.optional) {
+            w.field(l2, 12, 12);                       // statistics
+            statistics_optional(w, m);
+        } else if (m.has_stats) {
             w.field(l2, 12, 12);                       // statistics
             statistics(w, m.mn, m.mx);
         }
@@ -185,6 +209,56 @@ bool minmax_bytes(const double* v, int64_t n, std::string& mn,
     return true;
 }
 
+struct MetricRG {
+    int64_t num_rows;
+    ChunkMeta cols[5];
+};
+
+// FileMetaData of the 5-column metric layout, footer length and magic.
+bool metric_footer(FILE* f, const std::vector<MetricRG>& rgs, int64_t n,
+                   bool value_optional) {
+    TW w;
+    int16_t last = 0;
+    w.i32(last, 1, 1);  // version
+    w.list_header(last, 2, 12, 6);  // schema: root + 5 leaves
+    {
+        int16_t l2 = 0;   // root group
+        w.str(l2, 4, "schema");
+        w.i32(l2, 5, 5);  // num_children
+        w.stop();
+    }
+    for (int c = 0; c < 5; c++)
+        schema_element(w, kCols[c], value_optional && c == 2);
+    w.i64f(last, 3, n);  // num_rows
+    w.list_header(last, 4, 12, rgs.size());
+    for (const auto& rg : rgs) {
+        int16_t l2 = 0;
+        w.list_header(l2, 1, 12, 5);
+        int64_t total = 0;
+        for (int c = 0; c < 5; c++) total += rg.cols[c].total_size;
+        for (int c = 0; c < 5; c++)
+            column_chunk(w, kCols[c].name, kCols[c].physical, rg.cols[c]);
+        w.i64f(l2, 2, total);        // total_byte_size
+        w.i64f(l2, 3, rg.num_rows);  // num_rows
+        w.stop();
+    }
+    w.str(last, 6, "horaedb-amd hx_compact writer");
+    // column_orders: TYPE_ORDER for every leaf — required for readers to
+    // trust min_value/max_value (parquet.thrift ColumnOrder union)
+    w.list_header(last, 7, 12, 5);
+    for (int c = 0; c < 5; c++) {
+        int16_t l2 = 0;
+        w.field(l2, 1, 12);  // TypeDefinedOrder (empty struct)
+        w.stop();
+        w.stop();
+    }
+    w.stop();
+
+    uint32_t flen = (uint32_t)w.buf.size();
+    return fwrite(w.buf.data(), 1, flen, f) == flen &&
+           fwrite(&flen, 4, 1, f) == 1 && fwrite("PAR1", 1, 4, f) == 4;
+}
+
 }  // namespace
 
 std::string write_metric_sst(const std::string& path, const uint64_t* series,
@@ -203,11 +277,7 @@ std::string write_metric_sst(const std::string& path, const uint64_t* series,
 
     std::vector<uint64_t> seq_col;   // constant per file (closure precondition)
     std::vector<uint64_t> zeros;
-    struct RG {
-        int64_t num_rows;
-        ChunkMeta cols[5];
-    };
-    std::vector<RG> rgs;
+    std::vector<MetricRG> rgs;
     for (int64_t base = 0; base < n; base += row_group) {
         int64_t rows = std::min<int64_t>(row_group, n - base);
         if ((int64_t)seq_col.size() < rows) {
@@ -216,7 +286,7 @@ std::string write_metric_sst(const std::string& path, const uint64_t* series,
         }
         const void* data[5] = {series + base, ts + base, value + base,
                                seq_col.data(), zeros.data()};
-        RG rg;
+        MetricRG rg;
         rg.num_rows = rows;
         for (int c = 0; c < 5; c++) {
             int32_t payload = int32_t(rows * 8);
@@ -246,48 +316,87 @@ std::string write_metric_sst(const std::string& path, const uint64_t* series,
         rgs.push_back(rg);
     }
 
-    // footer: FileMetaData
-    TW w;
-    int16_t last = 0;
-    w.i32(last, 1, 1);  // version
-    w.list_header(last, 2, 12, 6);  // schema: root + 5 leaves
-    {
-        int16_t l2 = 0;   // root group
-        w.str(l2, 4, "schema");
-        w.i32(l2, 5, 5);  // num_children
-        w.stop();
-    }
-    for (const auto& c : kCols) schema_element(w, c);
-    w.i64f(last, 3, n);  // num_rows
-    w.list_header(last, 4, 12, rgs.size());
-    for (const auto& rg : rgs) {
-        int16_t l2 = 0;
-        w.list_header(l2, 1, 12, 5);
-        int64_t total = 0;
-        for (int c = 0; c < 5; c++) total += rg.cols[c].total_size;
-        for (int c = 0; c < 5; c++)
-            column_chunk(w, kCols[c].name, kCols[c].physical, rg.cols[c]);
-        w.i64f(l2, 2, total);        // total_byte_size
-        w.i64f(l2, 3, rg.num_rows);  // num_rows
-        w.stop();
-    }
-    w.str(last, 6, "horaedb-amd hx_compact writer");
-    // column_orders: TYPE_ORDER for every leaf — required for readers to
-    // trust min_value/max_value (parquet.thrift ColumnOrder union)
-    w.list_header(last, 7, 12, 5);
-    for (int c = 0; c < 5; c++) {
-        int16_t l2 = 0;
-        w.field(l2, 1, 12);  // TypeDefinedOrder (empty struct)
-        w.stop();
-        w.stop();
-    }
-    w.stop();
-
-    uint32_t flen = (uint32_t)w.buf.size();
-    if (fwrite(w.buf.data(), 1, flen, f) != flen) return fail("write failed");
-    if (fwrite(&flen, 4, 1, f) != 1) return fail("write failed");
-    if (fwrite("PAR1", 1, 4, f) != 4) return fail("write failed");
+    if (!metric_footer(f, rgs, n, false)) return fail("write failed");
     if (fclose(f) != 0) return "write_metric_sst: close failed";
+    return "";
+}
+
+std::string write_metric_sst_nullable(const std::string& path,
+                                      const uint64_t* series,
+                                      const int64_t* ts,
+                                      const NullableValues& value,
+                                      const uint64_t* seqs, uint64_t seq,
+                                      int64_t n, int64_t row_group) {
+    if (n <= 0) return "write_metric_sst_nullable: no rows";
+    if (row_group <= 0 || row_group % 64)
+        return "write_metric_sst_nullable: row_group is not a multiple of 64";
+    const int64_t wpg = row_group / 64;
+    for (int64_t g = 0, base = 0; base < n; g++, base += row_group)
+        if (value.n_valid[g] > std::min<int64_t>(row_group, n - base))
+            return "write_metric_sst_nullable: n_valid above the row count";
+    FILE* f = fopen(path.c_str(), "wb");
+    if (!f) return "write_metric_sst_nullable: cannot open " + path;
+    auto fail = [&](const char* m) {
+        fclose(f);
+        remove(path.c_str());
+        return std::string(m);
+    };
+    if (fwrite("PAR1", 1, 4, f) != 4) return fail("write failed");
+    int64_t off = 4;
+
+    std::vector<uint64_t> seq_col, zeros;
+    std::vector<uint8_t> levels;
+    std::vector<MetricRG> rgs;
+    for (int64_t g = 0, base = 0; base < n; g++, base += row_group) {
+        const int64_t rows = std::min<int64_t>(row_group, n - base);
+        if (!seqs && (int64_t)seq_col.size() < rows) seq_col.assign(rows, seq);
+        if ((int64_t)zeros.size() < rows) zeros.assign(rows, 0);
+        const int64_t nv = value.n_valid[g];
+        const uint64_t* packed = value.packed + base;
+        levels.clear();
+        encode_def_levels(value.bitmap_words + g * wpg, (uint32_t)rows,
+                          (uint32_t)nv, levels);
+        const void* data[5] = {series + base, ts + base, packed,
+                               seqs ? seqs + base : seq_col.data(),
+                               zeros.data()};
+        MetricRG rg;
+        rg.num_rows = rows;
+        for (int c = 0; c < 5; c++) {
+            const int64_t body = (c == 2 ? nv : rows) * 8;
+            const int32_t payload =
+                int32_t(body + (c == 2 ? (int64_t)levels.size() : 0));
+            auto hdr = page_header((int32_t)rows, payload);
+            ChunkMeta& m = rg.cols[c];
+            m.data_page_offset = off;
+            m.num_values = rows;
+            m.total_size = int64_t(hdr.size()) + payload;
+            switch (c) {
+                case 0: case 3: case 4:
+                    minmax_bytes((const uint64_t*)data[c], rows, m.mn, m.mx);
+                    break;
+                case 1:
+                    minmax_bytes((const int64_t*)data[c], rows, m.mn, m.mx);
+                    break;
+                case 2:
+                    m.optional = true;
+                    m.null_count = rows - nv;
+                    m.has_stats = minmax_bytes((const double*)data[c], nv,
+                                               m.mn, m.mx);
+                    break;
+            }
+            if (fwrite(hdr.data(), 1, hdr.size(), f) != hdr.size())
+                return fail("write failed");
+            if (c == 2 && fwrite(levels.data(), 1, levels.size(), f) !=
+                              levels.size())
+                return fail("write failed");
+            if (body && fwrite(data[c], 1, size_t(body), f) != size_t(body))
+                return fail("write failed");
+            off += m.total_size;
+        }
+        rgs.push_back(rg);
+    }
+    if (!metric_footer(f, rgs, n, true)) return fail("write failed");
+    if (fclose(f) != 0) return "write_metric_sst_nullable: close failed";
     return "";
 }
 

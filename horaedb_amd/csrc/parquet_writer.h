@@ -18,6 +18,31 @@ std::string write_metric_sst(const std::string& path, const uint64_t* series,
                              const int64_t* ts, const double* value,
                              uint64_t seq, int64_t n, int64_t row_group);
 
+// Nullable form of the metric writer: the `value` column is declared OPTIONAL
+// (the reference's shape for it), the four others stay REQUIRED. The values
+// come row-group-major, as kernel 1d (k_pack_optional) and
+// hx::pack_optional_host leave them: row group g covers rows
+// [g * row_group, min(n, (g + 1) * row_group)); row_group is a multiple of 64.
+struct NullableValues {
+    const uint64_t* packed;        // packed + g * row_group: n_valid[g]
+                                   // present values in row order, 64 bits each
+    const uint64_t* bitmap_words;  // + g * (row_group / 64): LSB-first, 1 =
+                                   // present, bits at and above the row
+                                   // group's row count zero
+    const uint32_t* n_valid;       // per row group
+};
+// Every value page is {level block, n_valid * 8 PLAIN bytes} with
+// DataPageHeader.num_values = rows; statistics always carry null_count, and
+// min/max over the present values by the DOUBLE rules (none for a chunk
+// without a non-NaN value). seqs: per-row __seq__ values, or NULL for the
+// constant `seq`.
+std::string write_metric_sst_nullable(const std::string& path,
+                                      const uint64_t* series,
+                                      const int64_t* ts,
+                                      const NullableValues& value,
+                                      const uint64_t* seqs, uint64_t seq,
+                                      int64_t n, int64_t row_group);
+
 // General flat-table writer (same page/footer layout) for the auxiliary
 // tables the RFC defines (metrics/series/tags/index,
 // docs/rfcs/20240827-metric-engine.md:86-137). Fixed 8-byte columns

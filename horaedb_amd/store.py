@@ -114,6 +114,20 @@ def _load():
     lib.hx_write_sst.argtypes = [C.c_char_p, C.POINTER(C.c_uint64),
                                  C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                  C.c_uint64, C.c_int64, C.c_int64]
+    lib.hx_set_nullable_values.argtypes = [C.c_void_p, C.c_int32]
+    lib.hx_write_nullable.argtypes = [
+        C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int64),
+        C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.c_int64, C.c_int32,
+        C.POINTER(C.c_uint64)]
+    lib.hx_write_sst_nullable.argtypes = [
+        C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int64),
+        C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.c_uint64, C.c_int64,
+        C.c_int64]
+    lib.hx_debug_pack_optional.argtypes = [
+        C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint8),
+        C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32,
+        C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
+        C.POINTER(C.c_uint64)]
     lib.hx_schema.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t),
                               C.POINTER(C.c_size_t)]
     lib.hx_catalog_size.argtypes = [C.c_void_p, C.POINTER(C.c_size_t)]
@@ -420,13 +434,29 @@ class Store:
             _lib.hx_tsids_free(out)
         return res
 
-    def write(self, series, ts, value, enable_check=True):
+    def set_nullable_values(self, on):
+        """Writer setting (hx_set_nullable_values): True makes every SST this
+        store writes declare `value` OPTIONAL and keeps null values through
+        write(valid=...), compact and compact_files."""
+        _check(_lib.hx_set_nullable_values(self._h, 1 if on else 0))
+
+    def write(self, series, ts, value, enable_check=True, valid=None):
         """ColumnarStorage::write (storage.rs:76-89): stable PK sort + new
-        SST + catalog add. Returns the new file's sequence."""
+        SST + catalog add. Returns the new file's sequence. valid: bool
+        array, False = the row's value is null (hx_write_nullable)."""
         series = np.ascontiguousarray(series, dtype=np.uint64)
         ts_a = np.ascontiguousarray(ts, dtype=np.int64)
         value = np.ascontiguousarray(value, dtype=np.float64)
         out = C.c_uint64()
+        if valid is not None:
+            bits = _validity_bits(valid, len(series))
+            _check(_lib.hx_write_nullable(
+                self._h, series.ctypes.data_as(C.POINTER(C.c_uint64)),
+                ts_a.ctypes.data_as(C.POINTER(C.c_int64)),
+                value.ctypes.data_as(C.POINTER(C.c_double)),
+                bits.ctypes.data_as(C.POINTER(C.c_uint8)), len(series),
+                1 if enable_check else 0, C.byref(out)))
+            return out.value
         _check(_lib.hx_write(
             self._h, series.ctypes.data_as(C.POINTER(C.c_uint64)),
             ts_a.ctypes.data_as(C.POINTER(C.c_int64)),
@@ -549,6 +579,66 @@ def write_sst_native(path, series, ts, value, seq, row_group=8192):
         path.encode(), series.ctypes.data_as(C.POINTER(C.c_uint64)),
         ts.ctypes.data_as(C.POINTER(C.c_int64)),
         value.ctypes.data_as(C.POINTER(C.c_double)), seq, n, row_group))
+
+
+def _validity_bits(valid, n):
+    """bool array -> LSB-first bitmap bytes (1 = value present)."""
+    valid = np.asarray(valid, dtype=bool)
+    if valid.shape != (n,):
+        raise ValueError("valid: one bool per row")
+    return np.ascontiguousarray(np.packbits(valid, bitorder="little"))
+
+
+def write_sst_native_nullable(path, series, ts, value, seq, valid=None,
+                              row_group=8192):
+    """Nullable twin of write_sst_native (hx_write_sst_nullable): `value`
+    is written OPTIONAL; valid is a bool array (False = null) or None."""
+    series = np.ascontiguousarray(series, dtype=np.uint64)
+    ts = np.ascontiguousarray(ts, dtype=np.int64)
+    value = np.ascontiguousarray(value, dtype=np.float64)
+    n = len(series)
+    bits = None if valid is None else _validity_bits(valid, n)
+    _check(_lib.hx_write_sst_nullable(
+        path.encode(), series.ctypes.data_as(C.POINTER(C.c_uint64)),
+        ts.ctypes.data_as(C.POINTER(C.c_int64)),
+        value.ctypes.data_as(C.POINTER(C.c_double)),
+        None if bits is None else bits.ctypes.data_as(C.POINTER(C.c_uint8)),
+        seq, n, row_group))
+
+
+def pack_optional(values, n, row_group, valid_words=None, valid_bits=None,
+                  perm=None):
+    """Kernel 1d through the test hook hx_debug_pack_optional (needs a GPU).
+    values: the source rows' 8-byte values (any 8-byte dtype); valid_words
+    (uint64 0/1 per source row) or valid_bits (LSB-first uint8 bitmap) or
+    neither; perm: uint32 source row per output row, or None. Returns
+    (packed uint64[n], bitmap uint64[groups * row_group / 64],
+    n_valid uint32[groups], n_errors)."""
+    values = np.ascontiguousarray(values).view(np.uint64)
+    n_src = len(values)
+    groups = (n + row_group - 1) // row_group if row_group > 0 else 0
+    packed = np.zeros(n, dtype=np.uint64)
+    bitmap = np.zeros(groups * (row_group // 64), dtype=np.uint64)
+    n_valid = np.zeros(groups, dtype=np.uint32)
+    errs = C.c_uint64()
+    keep = []
+
+    def ptr(a, dtype, ctype):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=dtype)
+        keep.append(a)
+        return a.ctypes.data_as(C.POINTER(ctype))
+
+    _check(_lib.hx_debug_pack_optional(
+        values.ctypes.data_as(C.POINTER(C.c_uint64)),
+        ptr(valid_words, np.uint64, C.c_uint64),
+        ptr(valid_bits, np.uint8, C.c_uint8),
+        ptr(perm, np.uint32, C.c_uint32), n_src, n, row_group,
+        packed.ctypes.data_as(C.POINTER(C.c_uint64)),
+        bitmap.ctypes.data_as(C.POINTER(C.c_uint64)),
+        n_valid.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(errs)))
+    return packed, bitmap, n_valid, errs.value
 
 
 def page_levels(path, row_group, column, max_rows=1 << 20):

@@ -37,7 +37,10 @@ enum {
     HX_ERR_UNSUPPORTED= 3,   /* encoding/codec outside round-1 scope; nulls
                                 in series_id/timestamp/__seq__, in a
                                 dictionary-encoded or Binary value column,
-                                under Append mode, or in compaction inputs */
+                                under Append mode; null values reaching the
+                                write side (compaction inputs, a zero bit
+                                given to hx_write_nullable) of a handle
+                                that has not set hx_set_nullable_values   */
     HX_ERR_NO_GPU     = 4,   /* HIP runtime/device unavailable */
     HX_ERR_HIP        = 5,   /* HIP call failed (see hx_last_error) */
     HX_ERR_INVALID    = 6,   /* bad argument */
@@ -101,6 +104,12 @@ enum {
  * run over the non-null survivors: sum/min/max/avg ignore nulls and count
  * counts values. A group all of whose surviving values are null is not
  * emitted (the result table has no validity channel).
+ * Write side: a handle writes REQUIRED columns and refuses null values
+ * (HX_ERR_UNSUPPORTED, nothing written or unlinked) until
+ * hx_set_nullable_values(h, 1); from then on every SST it writes declares
+ * `value` OPTIONAL, hx_write_nullable ingests null rows, and hx_compact /
+ * hx_compact_files keep a surviving null as a null row — it is still the
+ * winner of its PK and goes on shadowing older values in other files.
  *
  * Value domain (every f64 bit pattern is data: NaN of either sign and any
  * payload — the Prometheus stale marker 0x7FF0000000000002 is a signalling
@@ -272,6 +281,35 @@ hx_status hx_set_update_mode(hx_handle*, int32_t mode);
 hx_status hx_write(hx_handle*, const uint64_t* series, const int64_t* ts,
                    const double* value, int64_t n_rows, int32_t enable_check,
                    uint64_t* out_seq);
+
+/* Writer setting, per handle like hx_set_update_mode; default 0. 0: nothing
+ * this handle does changes — same files, same refusals. 1: every SST the
+ * handle writes (hx_write, hx_write_nullable, hx_compact, hx_compact_files)
+ * declares `value` OPTIONAL, the reference's shape for that column (a page
+ * without nulls carries one RLE run of definition levels), and null values
+ * are written as null rows instead of being refused. The four other columns
+ * stay REQUIRED. Not for stores with a Binary value column. */
+hx_status hx_set_nullable_values(hx_handle*, int32_t on);
+
+/* hx_write with missing samples (the reference's Arrow batches can carry
+ * them, types.rs:178-179). validity: LSB-first bitmap of n_rows bits, 1 =
+ * value present; NULL = all present. The 8 bytes of value[] at a null row
+ * are ignored. Validity follows its row through the stable PK sort, so of an
+ * equal-PK pair the later row of the batch wins, null or not. A zero bit
+ * while the handle's setting is 0 returns HX_ERR_UNSUPPORTED and writes
+ * nothing; without one the call is hx_write. */
+hx_status hx_write_nullable(hx_handle*, const uint64_t* series,
+                            const int64_t* ts, const double* value,
+                            const uint8_t* validity, int64_t n_rows,
+                            int32_t enable_check, uint64_t* out_seq);
+
+/* Nullable twin of hx_write_sst (no GPU needed): `value` OPTIONAL, validity
+ * as for hx_write_nullable, rows written in the order given. row_group must
+ * be a multiple of 64 (HX_ERR_INVALID otherwise). */
+hx_status hx_write_sst_nullable(const char* path, const uint64_t* series,
+                                const int64_t* ts, const double* value,
+                                const uint8_t* validity, uint64_t seq,
+                                int64_t n_rows, int64_t row_group);
 
 /* Native SST writer (the compaction output path; PLAIN uncompressed,
  * row-group 8192 contract — storage.rs:193-298). Exposed for tests/ingest. */
