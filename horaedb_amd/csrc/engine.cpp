@@ -10,6 +10,7 @@
 #include "../../include/horaedb_hx.h"
 #include "parquet_meta.h"
 #include "parquet_writer.h"
+#include "snappy_compress.h"
 #include "hx_device.h"
 
 #include <hip/hip_runtime.h>
@@ -96,6 +97,9 @@ struct hx_handle {
     int32_t nullable_values = 0;         // writer setting: 1 = every SST this
                                          // handle writes declares `value`
                                          // OPTIONAL (hx_set_nullable_values)
+    int32_t write_codec = 0;             // writer setting: page codec of
+                                         // every SST this handle writes
+                                         // (hx_set_write_codec)
     std::vector<CatSst> ssts;            // ascending seq
     std::vector<hx_sst_desc> find_out;   // scratch for hx_find_ssts
 };
@@ -281,6 +285,19 @@ extern "C" hx_status hx_set_nullable_values(hx_handle* h, int32_t on) {
         return fail(HX_ERR_UNSUPPORTED,
                     "nullable values need an f64 value column");
     h->nullable_values = on;
+    return HX_OK;
+}
+
+// Writer setting: the page codec of every SST the handle writes from now on
+// (the reference's config.rs:120-133 default is Snappy). 0 launches and
+// writes exactly what it always did.
+extern "C" hx_status hx_set_write_codec(hx_handle* h, int32_t codec) {
+    if (!h || (codec != HX_CODEC_NONE && codec != HX_CODEC_SNAPPY))
+        return fail(HX_ERR_INVALID, "write codec: 0 none / 1 snappy");
+    if (codec != HX_CODEC_NONE && h->bytes_value)
+        return fail(HX_ERR_UNSUPPORTED,
+                    "a write codec needs an f64 value column");
+    h->write_codec = codec;
     return HX_OK;
 }
 
@@ -2106,6 +2123,71 @@ extern "C" hx_status hx_debug_pack_optional(
     return HX_OK;
 }
 
+extern "C" hx_status hx_debug_snappy_compress(
+    const uint8_t* pages, const uint64_t* offs, const uint32_t* lens,
+    uint32_t n_pages, const uint32_t* src_align, uint8_t* out,
+    const uint64_t* out_offs, uint32_t* out_lens, uint64_t* n_errors) {
+    if (!n_errors || !out_offs ||
+        (n_pages && (!pages || !offs || !lens || !src_align || !out ||
+                     !out_lens)))
+        return fail(HX_ERR_INVALID, "null argument");
+    *n_errors = 0;
+    if (n_pages == 0) return HX_OK;
+    std::vector<hx::SnappyCompDesc> descs(n_pages);
+    size_t src_bytes = 0;
+    for (uint32_t i = 0; i < n_pages; i++) {
+        if (src_align[i] > 63 || out_offs[i + 1] < out_offs[i] ||
+            out_offs[i + 1] - out_offs[i] > 0xFFFFFFFFull)
+            return fail(HX_ERR_INVALID, "bad src_align or out_offs");
+        descs[i].src_off = align64(src_bytes) + src_align[i];
+        descs[i].dst_off = out_offs[i];
+        descs[i].n = lens[i];
+        descs[i].dst_cap = uint32_t(out_offs[i + 1] - out_offs[i]);
+        src_bytes = descs[i].src_off + lens[i];
+    }
+    const size_t out_bytes = out_offs[n_pages];
+    std::vector<uint8_t> h_src(src_bytes, 0);
+    for (uint32_t i = 0; i < n_pages; i++)
+        if (lens[i])
+            std::memcpy(h_src.data() + descs[i].src_off, pages + offs[i],
+                        lens[i]);
+    struct DevBufs {
+        void* p[5] = {};
+        ~DevBufs() {
+            for (void* q : p)
+                if (q) (void)hipFree(q);
+        }
+    } dev;
+    // every buffer exactly as large as the contract says it is
+    HIP_TRY(hipMalloc(&dev.p[0], std::max<size_t>(src_bytes, 1)));
+    HIP_TRY(hipMalloc(&dev.p[1], std::max<size_t>(out_bytes, 1)));
+    HIP_TRY(hipMalloc(&dev.p[2], size_t(n_pages) * sizeof(descs[0])));
+    HIP_TRY(hipMalloc(&dev.p[3], size_t(n_pages) * 4));
+    HIP_TRY(hipMalloc(&dev.p[4], 8));
+    if (src_bytes)
+        HIP_TRY(hipMemcpy(dev.p[0], h_src.data(), src_bytes,
+                          hipMemcpyHostToDevice));
+    if (out_bytes) HIP_TRY(hipMemset(dev.p[1], 0xEE, out_bytes));
+    HIP_TRY(hipMemcpy(dev.p[2], descs.data(),
+                      size_t(n_pages) * sizeof(descs[0]),
+                      hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(dev.p[3], 0xEE, size_t(n_pages) * 4));
+    HIP_TRY(hipMemset(dev.p[4], 0, 8));
+    HIP_TRY(hx::launch_snappy_compress(
+        nullptr, (const uint8_t*)dev.p[0], (uint8_t*)dev.p[1],
+        (const hx::SnappyCompDesc*)dev.p[2], n_pages, (uint32_t*)dev.p[3],
+        (unsigned long long*)dev.p[4]));
+    HIP_TRY(hipDeviceSynchronize());
+    if (out_bytes)
+        HIP_TRY(hipMemcpy(out, dev.p[1], out_bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_lens, dev.p[3], size_t(n_pages) * 4,
+                      hipMemcpyDeviceToHost));
+    unsigned long long errs = 0;
+    HIP_TRY(hipMemcpy(&errs, dev.p[4], 8, hipMemcpyDeviceToHost));
+    *n_errors = errs;
+    return HX_OK;
+}
+
 extern "C" hx_status hx_scan_agg(hx_handle* h, const hx_scan_spec* spec,
                                  const hx_agg_spec* agg,
                                  const hx_device_set* devs,
@@ -2401,6 +2483,123 @@ struct PackedValues {
     }
 };
 
+// Snappy streams of a file's pages, made on the device (kernel 1e) and
+// brought to the host in one copy; `ready` is the table the writers take.
+struct DeviceStreams {
+    std::vector<uint8_t> bytes;
+    std::vector<hx::PagePayload> ready;   // [row group * 5 + file column]
+    bool on_device[5] = {};               // the column's rows stayed there
+    size_t d2h_bytes = 0;                 // lengths, statistics and streams
+};
+
+// Kernel 1e over the kRowGroup-row slices of the columns that sit on the
+// device: col_words[c] is file column c's offset in 8-byte words from d_base
+// (n rows each), or -1 for a column the writer compresses itself. Then the
+// scan-and-pack pass, the lengths and one contiguous D2H of the streams.
+// k_page_minmax gives every page's footer statistics, so the rows of these
+// columns need not cross PCIe at all (out.on_device).
+// after_pack (may be null) is recorded behind the pack kernel. A page the
+// kernel refused is an error: the slots here are at Snappy's bound.
+hipError_t compress_columns_device(hipStream_t s, const uint8_t* d_base,
+                                   const int64_t col_words[5], uint32_t n,
+                                   hipEvent_t after_pack, DeviceStreams& out) {
+    const size_t n_groups = (size_t(n) + kRowGroup - 1) / kRowGroup;
+    std::vector<hx::SnappyCompDesc> descs;
+    std::vector<uint32_t> entry;   // ready-table index of page i
+    std::vector<uint32_t> kinds;   // the page's order, for its statistics
+    const uint32_t col_kind[5] = {hx::PAGE_ORDER_U64, hx::PAGE_ORDER_I64,
+                                  hx::PAGE_ORDER_F64, hx::PAGE_ORDER_U64,
+                                  hx::PAGE_ORDER_U64};
+    size_t slot_bytes = 0;
+    for (int c = 0; c < 5; c++) {
+        if (col_words[c] < 0) continue;
+        for (size_t g = 0; g < n_groups; g++) {
+            const size_t row0 = g * size_t(kRowGroup);
+            const size_t rows = std::min<size_t>(kRowGroup, n - row0);
+            hx::SnappyCompDesc d;
+            d.src_off = (uint64_t(col_words[c]) + row0) * 8;
+            d.n = uint32_t(rows * 8);
+            d.dst_cap = uint32_t(hx::snappy_max_compressed(d.n));
+            d.dst_off = slot_bytes;
+            slot_bytes = align64(slot_bytes + d.dst_cap);
+            descs.push_back(d);
+            entry.push_back(uint32_t(g * 5 + size_t(c)));
+            kinds.push_back(col_kind[c]);
+        }
+    }
+    for (int c = 0; c < 5; c++) out.on_device[c] = col_words[c] >= 0;
+    out.ready.assign(n_groups * 5, hx::PagePayload{nullptr, 0, 0, 0, 0});
+    out.bytes.clear();
+    out.d2h_bytes = 0;
+    const uint32_t n_pages = uint32_t(descs.size());
+    if (n_pages == 0)   // nothing on the device: the pair closes empty
+        return after_pack ? hipEventRecord(after_pack, s) : hipSuccess;
+    // one allocation: slots, packed streams, descriptors, kinds, the scan's
+    // offsets, then what the host reads back first: lengths, error count,
+    // statistics
+    const size_t desc_bytes = align64(size_t(n_pages) * sizeof(descs[0]));
+    const size_t kind_bytes = align64(size_t(n_pages) * 4);
+    const size_t off_bytes = align64(size_t(n_pages) * 8);
+    // the error count sits behind the lengths, 8-byte aligned, the
+    // statistics behind it
+    const size_t err_word = (size_t(n_pages) * 4 + 7) / 8;
+    const size_t back_words =
+        err_word + 1 + size_t(n_pages) * (sizeof(hx::PageStat) / 8);
+    uint8_t* dev = nullptr;
+    hipError_t e = hipMalloc((void**)&dev, 2 * slot_bytes + desc_bytes +
+                                               kind_bytes + off_bytes +
+                                               back_words * 8);
+    if (e != hipSuccess) return e;
+    std::unique_ptr<void, void (*)(void*)> guard(
+        dev, [](void* q) { (void)hipFree(q); });
+    uint8_t* d_slots = dev;
+    uint8_t* d_packed = dev + slot_bytes;
+    auto* d_descs = (hx::SnappyCompDesc*)(d_packed + slot_bytes);
+    uint32_t* d_kinds = (uint32_t*)((uint8_t*)d_descs + desc_bytes);
+    auto* d_offs = (unsigned long long*)((uint8_t*)d_kinds + kind_bytes);
+    uint32_t* d_lens = (uint32_t*)((uint8_t*)d_offs + off_bytes);
+    unsigned long long* d_err = (unsigned long long*)d_lens + err_word;
+    hx::PageStat* d_stats = (hx::PageStat*)(d_err + 1);
+#define CS_TRY(x) do { e = (x); if (e != hipSuccess) return e; } while (0)
+    CS_TRY(hipMemcpyAsync(d_descs, descs.data(),
+                          size_t(n_pages) * sizeof(descs[0]),
+                          hipMemcpyHostToDevice, s));
+    CS_TRY(hipMemcpyAsync(d_kinds, kinds.data(), size_t(n_pages) * 4,
+                          hipMemcpyHostToDevice, s));
+    CS_TRY(hipMemsetAsync(d_err, 0, 8, s));
+    CS_TRY(hx::launch_snappy_compress(s, d_base, d_slots, d_descs, n_pages,
+                                      d_lens, d_err));
+    CS_TRY(hx::launch_page_minmax(s, d_base, d_descs, d_kinds, n_pages,
+                                  d_stats));
+    CS_TRY(hx::launch_snappy_pack(s, d_slots, d_descs, n_pages, d_lens,
+                                  d_offs, d_packed));
+    if (after_pack) CS_TRY(hipEventRecord(after_pack, s));
+    std::vector<uint64_t> lens_host(back_words);
+    CS_TRY(hipMemcpyAsync(lens_host.data(), d_lens, lens_host.size() * 8,
+                          hipMemcpyDeviceToHost, s));
+    CS_TRY(hipStreamSynchronize(s));
+    if (lens_host[err_word] != 0) return hipErrorUnknown;
+    const uint32_t* lens = (const uint32_t*)lens_host.data();
+    size_t total = 0;
+    for (uint32_t i = 0; i < n_pages; i++) total += lens[i];
+    out.bytes.resize(total);
+    CS_TRY(hipMemcpyAsync(out.bytes.data(), d_packed, total,
+                          hipMemcpyDeviceToHost, s));
+    CS_TRY(hipStreamSynchronize(s));
+#undef CS_TRY
+    const hx::PageStat* stats =
+        (const hx::PageStat*)(lens_host.data() + err_word + 1);
+    size_t at = 0;
+    for (uint32_t i = 0; i < n_pages; i++) {
+        out.ready[entry[i]] = hx::PagePayload{
+            out.bytes.data() + at, lens[i], stats[i].has ? 1u : 2u,
+            stats[i].min_bits, stats[i].max_bits};
+        at += lens[i];
+    }
+    out.d2h_bytes = lens_host.size() * 8 + total;
+    return hipSuccess;
+}
+
 // number of zero bits among the first n of an LSB-first bitmap
 int64_t count_nulls(const uint8_t* validity, int64_t n) {
     if (!validity) return 0;
@@ -2433,19 +2632,62 @@ extern "C" hx_status hx_write_sst_nullable(
     return HX_OK;
 }
 
+extern "C" hx_status hx_write_sst_codec(
+    const char* path, const uint64_t* series, const int64_t* ts,
+    const double* value, const uint8_t* validity, int32_t nullable,
+    uint64_t seq, int64_t n_rows, int64_t row_group, int32_t codec) {
+    if (!path || !series || !ts || !value || n_rows <= 0 || row_group <= 0)
+        return fail(HX_ERR_INVALID, "bad argument");
+    if (codec != HX_CODEC_NONE && codec != HX_CODEC_SNAPPY)
+        return fail(HX_ERR_INVALID, "write codec: 0 none / 1 snappy");
+    if (nullable != 0 && nullable != 1)
+        return fail(HX_ERR_INVALID, "nullable: 0 REQUIRED / 1 OPTIONAL");
+    std::string err;
+    if (!nullable) {
+        if (validity)
+            return fail(HX_ERR_INVALID,
+                        "validity given for a REQUIRED value column");
+        err = hx::write_metric_sst(path, series, ts, value, seq, n_rows,
+                                   row_group, codec);
+    } else {
+        if (row_group % 64)
+            return fail(HX_ERR_INVALID, "row_group is not a multiple of 64");
+        PackedValues pv;
+        pv.resize(n_rows, row_group);
+        hx::pack_optional_host((const uint64_t*)value, validity, nullptr,
+                               (uint64_t)n_rows, (uint64_t)n_rows,
+                               (uint64_t)row_group, pv.packed.data(),
+                               pv.bitmap.data(), pv.n_valid.data());
+        err = hx::write_metric_sst_nullable(path, series, ts, pv.view(),
+                                            nullptr, seq, n_rows, row_group,
+                                            codec);
+    }
+    if (!err.empty()) return fail(HX_ERR_IO, err);
+    return HX_OK;
+}
+
+extern "C" uint64_t hx_debug_snappy_compress_host(const uint8_t* src,
+                                                  uint64_t n, uint8_t* dst,
+                                                  uint64_t cap) {
+    return hx::snappy_compress_host(src, size_t(n), dst, size_t(cap));
+}
+
 // GPU ingest sort (stable by (series, ts); equal PKs keep input order):
 // two stable LSD radix passes over a u32 permutation — ts (sign-biased),
 // then series — then a device gather and one D2H. Returns false on any HIP
 // error so the caller falls back to the host sort. With `pv` (nullable
 // writer) the validity bitmap is uploaded as it is, n / 8 bytes, the gather
 // takes series and ts only, and kernel 1d packs the values by the same
-// permutation; v2 is not written.
+// permutation; v2 is not written. With `streams` (write codec Snappy) kernel
+// 1e compresses the sorted columns where the gather left them — series, ts
+// and, in the REQUIRED form, value — and their streams come back too.
 static bool gpu_sort_batch(const uint64_t* series, const int64_t* ts,
                            const double* value, int64_t n,
                            std::vector<uint64_t>& s2, std::vector<int64_t>& t2,
                            std::vector<double>& v2,
                            const uint8_t* validity = nullptr,
-                           PackedValues* pv = nullptr) {
+                           PackedValues* pv = nullptr,
+                           DeviceStreams* streams = nullptr) {
     hipStream_t s = nullptr;
     uint8_t* dev = nullptr;
     void* d_temp = nullptr;
@@ -2511,8 +2753,10 @@ static bool gpu_sort_batch(const uint64_t* series, const int64_t* ts,
             d_dst + 2 * N, d_bm, d_nv, d_err));
         pv->resize(n, kRowGroup);
         unsigned long long errs = 0;
-        GS_TRY(hipMemcpyAsync(host.data(), d_dst, 3 * N * 8,
-                              hipMemcpyDeviceToHost, s));
+        // with streams only the packed values come back, series and ts stay
+        const size_t from = streams ? 2 * N : 0;
+        GS_TRY(hipMemcpyAsync(host.data() + from, d_dst + from,
+                              (3 * N - from) * 8, hipMemcpyDeviceToHost, s));
         GS_TRY(hipMemcpyAsync(pv->bitmap.data(), d_bm, bm_words * 8,
                               hipMemcpyDeviceToHost, s));
         GS_TRY(hipMemcpyAsync(pv->n_valid.data(), d_nv, n_groups * 4,
@@ -2523,14 +2767,25 @@ static bool gpu_sort_batch(const uint64_t* series, const int64_t* ts,
         std::memcpy(pv->packed.data(), host.data() + 2 * N, N * 8);
     } else {
         GS_TRY(hx::launch_gather_multi(s, srcs, 3, pc, d_dst, (uint32_t)N));
-        GS_TRY(hipMemcpyAsync(host.data(), d_dst, 3 * N * 8,
-                              hipMemcpyDeviceToHost, s));
-        GS_TRY(hipStreamSynchronize(s));
-        std::memcpy(v2.data(), host.data() + 2 * N, N * 8);
+        if (!streams) {   // with streams the three columns stay on the device
+            GS_TRY(hipMemcpyAsync(host.data(), d_dst, 3 * N * 8,
+                                  hipMemcpyDeviceToHost, s));
+            GS_TRY(hipStreamSynchronize(s));
+            std::memcpy(v2.data(), host.data() + 2 * N, N * 8);
+        }
+    }
+    if (streams) {
+        // the OPTIONAL value page opens with its level block: host twin
+        const int64_t col_words[5] = {0, (int64_t)N, pv ? -1 : 2 * (int64_t)N,
+                                      -1, -1};
+        GS_TRY(compress_columns_device(s, (const uint8_t*)d_dst, col_words,
+                                       (uint32_t)N, nullptr, *streams));
     }
 #undef GS_TRY
-    std::memcpy(s2.data(), host.data(), N * 8);
-    std::memcpy(t2.data(), host.data() + N, N * 8);
+    if (!streams) {
+        std::memcpy(s2.data(), host.data(), N * 8);
+        std::memcpy(t2.data(), host.data() + N, N * 8);
+    }
     if (d_temp) (void)hipFree(d_temp);
     (void)hipFree(dev);
     return true;
@@ -2580,10 +2835,15 @@ static hx_status write_batch(hx_handle* h, const uint64_t* series,
     // the device path, its host twin here)
     const bool nullable = h->nullable_values != 0;
     PackedValues pv;
+    const int32_t codec = h->write_codec;
+    DeviceStreams streams;   // codec Snappy on the device route, else empty:
+                             // the writer compresses with the host twin
     bool sorted_on_gpu = false;
     if (n >= (1 << 16) && hip_device_count() > 0) {
         sorted_on_gpu = gpu_sort_batch(series, ts, value, n, s2, t2, v2,
-                                       validity, nullable ? &pv : nullptr);
+                                       validity, nullable ? &pv : nullptr,
+                                       codec ? &streams : nullptr);
+        if (!sorted_on_gpu) streams = DeviceStreams();
     }
     if (!sorted_on_gpu) {
         std::vector<uint32_t> order(n);
@@ -2612,12 +2872,19 @@ static hx_status write_batch(hx_handle* h, const uint64_t* series,
     const uint64_t new_seq = max_seq + 1;
     std::string out_path = h->store + "/data/" + std::to_string(new_seq) +
                            ".sst";
+    const hx::PagePayload* ready =
+        streams.ready.empty() ? nullptr : streams.ready.data();
+    // a column kernel 1e compressed never came to the host: its pages and
+    // statistics are in `ready`
+    const uint64_t* w_series = streams.on_device[0] ? nullptr : s2.data();
+    const int64_t* w_ts = streams.on_device[1] ? nullptr : t2.data();
+    const double* w_value = streams.on_device[2] ? nullptr : v2.data();
     std::string werr =
-        nullable ? hx::write_metric_sst_nullable(out_path, s2.data(),
-                                                 t2.data(), pv.view(), nullptr,
-                                                 new_seq, n, kRowGroup)
-                 : hx::write_metric_sst(out_path, s2.data(), t2.data(),
-                                        v2.data(), new_seq, n, kRowGroup);
+        nullable ? hx::write_metric_sst_nullable(out_path, w_series, w_ts,
+                                                 pv.view(), nullptr, new_seq,
+                                                 n, kRowGroup, codec, ready)
+                 : hx::write_metric_sst(out_path, w_series, w_ts, w_value,
+                                        new_seq, n, kRowGroup, codec, ready);
     if (!werr.empty()) return fail(HX_ERR_IO, werr);
     CatSst fresh;
     hx_status st = read_file_meta(out_path, new_seq, fresh);
@@ -2669,6 +2936,7 @@ static hx_status compact_rows(hx_handle* h, hx_prepared* P,
                               uint64_t* out_new_seq) {
     DevPlan& plan = P->plans[0];
     const bool nullable = h->nullable_values != 0;
+    const int32_t codec = h->write_codec;
     // the REQUIRED writer cannot keep a null: dropping it would be data
     // loss. Refused before anything is written or unlinked.
     if (plan.has_nulls && !nullable)
@@ -2741,18 +3009,20 @@ static hx_status compact_rows(hx_handle* h, hx_prepared* P,
     const size_t nv_words = (n_groups + 1) / 2;   // u32 counts, in 8-byte units
     const size_t words = size_t(n_cols) * n +
                          (nullable ? bm_words + nv_words + 1 : 0);
-    std::vector<uint64_t> host(words);
+    // under Snappy without the nullable form nothing comes back raw
+    std::vector<uint64_t> host(!codec || nullable ? words : 0);
     unsigned long long* d_dst = nullptr;
     HIP_TRY(hipMalloc((void**)&d_dst, words * 8));
     std::unique_ptr<void, void (*)(void*)> dst_guard(
         d_dst, [](void* q) { (void)hipFree(q); });
-    // HX_DEBUG: HIP-event times of the final gather and of kernel 1d
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    // HX_DEBUG: HIP-event times of the final gather, of kernel 1d and of
+    // kernel 1e with its pack pass
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     const bool timed = getenv("HX_DEBUG") != nullptr;
     struct EvGuard {
         hipEvent_t* e;
         ~EvGuard() {
-            for (int i = 0; i < 3; i++)
+            for (int i = 0; i < 4; i++)
                 if (e[i]) (void)hipEventDestroy(e[i]);
         }
     } ev_guard{ev};
@@ -2790,28 +3060,66 @@ static hx_status compact_rows(hx_handle* h, hx_prepared* P,
         if (timed) HIP_TRY(hipEventRecord(ev[1], s));
     }
     if (timed) HIP_TRY(hipEventRecord(ev[2], s));
-    HIP_TRY(hipMemcpyAsync(host.data(), d_dst, words * 8,
-                           hipMemcpyDeviceToHost, s));
+    // Writer codec Snappy: kernel 1e over the 8192-row slices of the columns
+    // where they sit in d_dst (series, ts, per-row seq, and value in its
+    // REQUIRED form; an OPTIONAL value page opens with its level block and
+    // goes through the host twin), then scan-and-pack and one D2H of the
+    // streams. Codec 0 launches nothing here.
+    DeviceStreams streams;
+    if (codec) {
+        const int64_t col_words[5] = {
+            0, (int64_t)n, nullable ? -1 : 2 * (int64_t)n,
+            keep_seq ? 3 * (int64_t)n : -1, -1};
+        HIP_TRY(compress_columns_device(s, (const uint8_t*)d_dst, col_words,
+                                        n, timed ? ev[3] : nullptr, streams));
+    } else if (timed) {
+        HIP_TRY(hipEventRecord(ev[3], s));
+    }
+    // what still has to come back raw: everything under codec 0; under
+    // Snappy only what kernel 1e did not take — the packed values and, behind
+    // the columns, the bitmaps, counts and error word of the nullable form
+    size_t raw_bytes = 0;
+    auto bring = [&](size_t w0, size_t w1) {
+        raw_bytes += (w1 - w0) * 8;
+        return hipMemcpyAsync(host.data() + w0, d_dst + w0, (w1 - w0) * 8,
+                              hipMemcpyDeviceToHost, s);
+    };
+    if (!codec) {
+        HIP_TRY(bring(0, words));
+    } else if (nullable) {
+        HIP_TRY(bring(2 * size_t(n), 3 * size_t(n)));
+        HIP_TRY(bring(size_t(n_cols) * n, words));
+    }
     HIP_TRY(hipStreamSynchronize(s));
     dst_guard.reset();
     if (timed) {
-        float gather_ms = 0, pack_ms = 0;
+        float gather_ms = 0, pack_ms = 0, comp_ms = 0;
         HIP_TRY(hipEventElapsedTime(&gather_ms, ev[0], ev[1]));
         HIP_TRY(hipEventElapsedTime(&pack_ms, ev[1], ev[2]));
+        HIP_TRY(hipEventElapsedTime(&comp_ms, ev[2], ev[3]));
         fprintf(stderr,
                 "[hx] compact rows=%u cols_gathered=%u nullable=%d nulls=%d "
-                "gather_ms=%.4f pack_ms=%.4f d2h_bytes=%zu\n",
+                "codec=%d gather_ms=%.4f pack_ms=%.4f comp_ms=%.4f "
+                "d2h_bytes=%zu\n",
                 n, nullable ? n_cols - 1 : n_cols, int(nullable), int(nulls),
-                gather_ms, pack_ms, words * 8);
+                codec, gather_ms, pack_ms, comp_ms,
+                raw_bytes + streams.d2h_bytes);
     }
+    const hx::PagePayload* ready =
+        streams.ready.empty() ? nullptr : streams.ready.data();
 
     const uint64_t new_seq = max_seq + 1;  // fresh file id (sst.rs:39-46)
     std::string out_path = h->store + "/data/" + std::to_string(new_seq) +
                            ".sst";
-    const uint64_t* h_series = host.data();
-    const int64_t* h_ts = (const int64_t*)(host.data() + n);
-    const uint64_t* h_val = host.data() + 2 * size_t(n);
-    const uint64_t* h_seq = keep_seq ? host.data() + 3 * size_t(n) : nullptr;
+    // a column kernel 1e compressed never came to the host (null here): its
+    // pages and statistics are in `ready`
+    const uint64_t* h_series = streams.on_device[0] ? nullptr : host.data();
+    const int64_t* h_ts =
+        streams.on_device[1] ? nullptr : (const int64_t*)(host.data() + n);
+    const uint64_t* h_val =
+        streams.on_device[2] ? nullptr : host.data() + 2 * size_t(n);
+    const uint64_t* h_seq = keep_seq && !streams.on_device[3]
+                                ? host.data() + 3 * size_t(n) : nullptr;
     std::string werr;
     if (nullable) {
         const uint64_t* h_bm = host.data() + size_t(n_cols) * n;
@@ -2820,15 +3128,16 @@ static hx_status compact_rows(hx_handle* h, hx_prepared* P,
         hx::NullableValues nv{h_val, h_bm,
                               (const uint32_t*)(h_bm + bm_words)};
         werr = hx::write_metric_sst_nullable(out_path, h_series, h_ts, nv,
-                                             h_seq, new_seq, n, kRowGroup);
+                                             h_seq, new_seq, n, kRowGroup,
+                                             codec, ready);
     } else if (keep_seq) {
         werr = hx::write_metric_sst_seqs(out_path, h_series, h_ts,
                                          (const double*)h_val, h_seq, n,
-                                         kRowGroup);
+                                         kRowGroup, codec, ready);
     } else {
         werr = hx::write_metric_sst(out_path, h_series, h_ts,
                                     (const double*)h_val, new_seq, n,
-                                    kRowGroup);
+                                    kRowGroup, codec, ready);
     }
     if (!werr.empty()) return fail(HX_ERR_IO, werr);
 

@@ -202,6 +202,25 @@ struct SnappyPageDesc {
     uint32_t uncomp_len;
 };
 
+// Snappy compress unit (k_snappy_compress, DESIGN §4 kernel 1e): one page of
+// n bytes at src + src_off (any byte alignment) into the output slot
+// [dst + dst_off, + dst_cap); a slot below 32 + n + n / 6 is refused.
+struct SnappyCompDesc {
+    uint64_t src_off;
+    uint64_t dst_off;
+    uint32_t n;
+    uint32_t dst_cap;
+};
+
+// Statistics of one page of 8-byte values (k_page_minmax), as the Parquet
+// writer puts them into the footer. kind: the column's order.
+enum : uint32_t { PAGE_ORDER_U64 = 0, PAGE_ORDER_I64 = 1, PAGE_ORDER_F64 = 2 };
+struct PageStat {
+    uint64_t min_bits;
+    uint64_t max_bits;
+    uint64_t has;         // 0: no value enters the bounds (f64: NaN only)
+};
+
 // OPTIONAL-column PLAIN page unit (k_expand_optional, DESIGN §4 kernel 1c).
 // The page's n_valid packed 8-byte values start at src + lvl_bytes: a v1
 // page the Snappy decoder wrote to dec opens with its definition-level block

@@ -56,3 +56,25 @@ extern "C" hx_status hx_debug_pack_optional(
     const uint8_t* valid_bits, const uint32_t* perm, uint32_t n_src,
     uint32_t n, uint32_t row_group, uint64_t* packed_out,
     uint64_t* bitmap_out, uint32_t* n_valid_out, uint64_t* n_errors);
+
+// Test hook (exported, not part of the public C-ABI, no GPU needed): the host
+// twin of kernel 1e, hx::snappy_compress_host (snappy_compress.h). Returns
+// the stream's size, 0 when cap is below Snappy's bound 32 + n + n / 6.
+extern "C" uint64_t hx_debug_snappy_compress_host(const uint8_t* src,
+                                                  uint64_t n, uint8_t* dst,
+                                                  uint64_t cap);
+
+// Test hook (exported, not part of the public C-ABI): run the production
+// launch of kernel 1e (hx::launch_snappy_compress, hx_kernels.h) once over
+// n_pages caller-built pages on the current device. Page i is pages[offs[i],
+// offs[i] + lens[i]); it is uploaded at a 64-byte-aligned device address plus
+// src_align[i] (0..63). out_offs has n_pages + 1 ascending entries: page i's
+// output slot is [out_offs[i], out_offs[i + 1]) of one device buffer of
+// out_offs[n_pages] bytes, pre-filled with 0xEE and copied back whole into
+// out. out_lens[i] receives the stream's size (0 for a refused page);
+// *n_errors the number of pages whose slot was below 32 + n + n / 6. Every
+// device buffer is exactly as large as stated here.
+extern "C" hx_status hx_debug_snappy_compress(
+    const uint8_t* pages, const uint64_t* offs, const uint32_t* lens,
+    uint32_t n_pages, const uint32_t* src_align, uint8_t* out,
+    const uint64_t* out_offs, uint32_t* out_lens, uint64_t* n_errors);

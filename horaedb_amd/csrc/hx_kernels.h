@@ -48,6 +48,30 @@ hipError_t launch_pack_optional(hipStream_t s,
                                 unsigned long long* packed_out,
                                 uint64_t* bitmap_out, uint32_t* n_valid,
                                 unsigned long long* err_flag);
+// Kernel 1e, one wave per page: the Snappy stream of src[src_off, + n) goes to
+// dst[dst_off, ...) and its size to out_len[page]; the bytes are those of
+// hx::snappy_compress_host. A page whose dst_cap is below 32 + n + n / 6 is
+// counted in err_flag, gets out_len 0 and its slot is not written.
+hipError_t launch_snappy_compress(hipStream_t s, const uint8_t* src,
+                                  uint8_t* dst, const SnappyCompDesc* pages,
+                                  uint32_t n_pages, uint32_t* out_len,
+                                  unsigned long long* err_flag);
+// Behind it: an exclusive scan of out_len into offs (n_pages words of device
+// scratch), then stream i moves from its slot to packed + offs[i], so one
+// copy of sum(out_len) bytes brings every stream to the host.
+hipError_t launch_snappy_pack(hipStream_t s, const uint8_t* slots,
+                              const SnappyCompDesc* pages, uint32_t n_pages,
+                              const uint32_t* out_len,
+                              unsigned long long* offs, uint8_t* packed);
+// Footer statistics of the same pages (src_off a multiple of 8, n / 8
+// values each), one wave per page: min and max in the order kinds[page]
+// names. PAGE_ORDER_F64 follows the writer's DOUBLE rules: NaN never enters,
+// a zero bound comes out as min -0.0 / max +0.0, has = 0 without a non-NaN
+// value.
+hipError_t launch_page_minmax(hipStream_t s, const uint8_t* src,
+                              const SnappyCompDesc* pages,
+                              const uint32_t* kinds, uint32_t n_pages,
+                              PageStat* out);
 hipError_t launch_copy_u64(hipStream_t s, const uint8_t* blob, uint8_t* dec,
                            const CopyDesc* descs, uint32_t n_descs);
 // nulls: the plan staged a validity bitmap — launch the null-aware instance

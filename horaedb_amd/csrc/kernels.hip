@@ -7,6 +7,7 @@
 // north-star aggregate (no reference counterpart).
 #include <hip/hip_runtime.h>
 #include "hx_device.h"
+#include "snappy_emit.h"
 
 namespace hx {
 
@@ -2751,6 +2752,315 @@ k_iota(uint32_t* out, uint32_t n) {
         out[i] = i;
 }
 
+// ---------------------------------------------------------------------------
+// Kernel 1e: Snappy page compressor, the write side's twin of
+// k_snappy_decompress. One wave (one 64-thread block) per page; the 16 KB
+// hash table of position + 1 lives in LDS. The stream is a pure function of
+// the page bytes and equals hx::snappy_compress_host (snappy_compress.h),
+// whose header comment states the algorithm: each step examines the 64
+// positions [pos, pos + 64), one per lane, ranks each lane's candidates by a
+// prefix capped at 16 bytes, a ballot picks the first lane, the match is
+// extended 64 bytes per ballot, lane 0 writes the tags (snappy_emit.h, shared
+// with the twin) and the wave copies literal bytes. Table inserts are
+// atomicMax on the LDS word, consumed positions only.
+// Reads nothing outside src[0, n) (any byte alignment), writes nothing
+// outside dst[0, dst_cap); a slot below Snappy's bound 32 + n + n / 6 counts
+// one error, gets out_len 0 and is left untouched.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t sc_load32(const uint8_t* p) {
+    uint32_t w;
+    __builtin_memcpy(&w, p, 4);
+    return w;
+}
+__device__ __forceinline__ uint64_t sc_load64(const uint8_t* p) {
+    uint64_t w;
+    __builtin_memcpy(&w, p, 8);
+    return w;
+}
+
+// d and s congruent modulo sizeof(T): bytes up to d's alignment, T-wide
+// body, bytes at the end. nt threads, thread t of them.
+template <typename T>
+__device__ __forceinline__ void sc_copy_as(uint8_t* d, const uint8_t* s,
+                                           uint32_t len, uint32_t t,
+                                           uint32_t nt) {
+    uint32_t head = uint32_t(-(uintptr_t)d) & uint32_t(sizeof(T) - 1);
+    if (head > len) head = len;
+    if (t < head) d[t] = s[t];
+    const uint32_t body = (len - head) / uint32_t(sizeof(T));
+    const T* sv = (const T*)(s + head);
+    T* dv = (T*)(d + head);
+    for (uint32_t i = t; i < body; i += nt) dv[i] = sv[i];
+    const uint32_t done = head + body * uint32_t(sizeof(T));
+    if (t < len - done) d[done + t] = s[done + t];
+}
+
+// Cooperative copy of len bytes, non-overlapping, any alignment: the widest
+// access (up to 16 B per thread) that the distance between d and s allows.
+__device__ __forceinline__ void sc_copy(uint8_t* d, const uint8_t* s,
+                                        uint32_t len, uint32_t t,
+                                        uint32_t nt) {
+    const uint32_t diff = uint32_t((uintptr_t)d - (uintptr_t)s) | 16u;
+    const uint32_t width = diff & (0u - diff);   // lowest set bit: 1..16
+    if (len < 64 || width == 1) {
+        for (uint32_t i = t; i < len; i += nt) d[i] = s[i];
+    } else if (width == 16) {
+        sc_copy_as<uint4>(d, s, len, t, nt);
+    } else if (width == 8) {
+        sc_copy_as<uint2>(d, s, len, t, nt);
+    } else if (width == 4) {
+        sc_copy_as<uint32_t>(d, s, len, t, nt);
+    } else {
+        sc_copy_as<uint16_t>(d, s, len, t, nt);
+    }
+}
+
+__global__ void __launch_bounds__(64)
+k_snappy_compress(const uint8_t* __restrict__ src_base,
+                  uint8_t* __restrict__ dst_base,
+                  const SnappyCompDesc* __restrict__ pages, uint32_t n_pages,
+                  uint32_t* __restrict__ out_len,
+                  unsigned long long* err_flag) {
+    __shared__ uint32_t H[SNAPPY_HASH_SIZE];
+    const uint32_t lane = threadIdx.x;
+    for (uint32_t pg = blockIdx.x; pg < n_pages; pg += gridDim.x) {
+        const SnappyCompDesc pd = pages[pg];
+        const uint32_t N = pd.n;
+        const uint32_t cap = pd.dst_cap;
+        if ((uint64_t)cap < snappy_max_compressed(N)) {
+            if (lane == 0) {
+                atomicAdd(err_flag, 1ull);
+                out_len[pg] = 0;
+            }
+            continue;
+        }
+        const uint8_t* src = src_base + pd.src_off;
+        uint8_t* dst = dst_base + pd.dst_off;
+        __syncthreads();   // the previous page's table reads are done
+        for (uint32_t i = lane; i < SNAPPY_HASH_SIZE; i += 64) H[i] = 0;
+        __syncthreads();
+
+        // lane 0 writes tag bytes; their count goes to every lane
+        uint32_t k = 0;
+        if (lane == 0) k = snappy_emit_varint(dst, N);
+        uint32_t o = __shfl(k, 0);
+        bool overflow = false;
+        // literal [from, to), to > from
+        auto emit_literal = [&](uint32_t from, uint32_t to) {
+            const uint32_t len = to - from;
+            if ((uint64_t)o + 5 + len > cap) {
+                overflow = true;
+                return;
+            }
+            uint32_t kk = 0;
+            if (lane == 0) kk = snappy_emit_literal_tag(dst + o, len);
+            o += __shfl(kk, 0);
+            sc_copy(dst + o, src + from, len, lane, 64);
+            o += len;
+        };
+
+        uint32_t pos = 0, lit_start = 0;
+        while ((uint64_t)pos + 4 <= N && !overflow) {
+            const uint32_t end =
+                N - 3 - pos < SNAPPY_CHUNK ? N - 3 : pos + SNAPPY_CHUNK;
+            const uint32_t p = pos + lane;
+            const bool active = p < end;
+            uint32_t w = 0, best_len = 0, best_c = 0;
+            if (active) {
+                w = sc_load32(src + p);
+                const uint32_t lim =
+                    N - p < SNAPPY_PROBE_CAP ? N - p : SNAPPY_PROBE_CAP;
+                const bool full = lim == SNAPPY_PROBE_CAP;
+                uint64_t a0 = 0, a1 = 0;
+                if (full) {
+                    a0 = sc_load64(src + p);
+                    a1 = sc_load64(src + p + 8);
+                }
+                auto probe = [&](uint32_t c) {
+                    uint32_t len;
+                    if (full) {   // c + 16 < p + 16 <= N
+                        const uint64_t x = a0 ^ sc_load64(src + c);
+                        if ((uint32_t)x) return;
+                        if (x) {
+                            len = uint32_t(__builtin_ctzll(x)) >> 3;
+                        } else {
+                            const uint64_t y = a1 ^ sc_load64(src + c + 8);
+                            len = 8 + (y ? uint32_t(__builtin_ctzll(y)) >> 3
+                                         : 8u);
+                        }
+                    } else {
+                        if (sc_load32(src + c) != w) return;
+                        len = 4;
+                        while (len < lim && src[c + len] == src[p + len])
+                            len++;
+                    }
+                    if (len > best_len || (len == best_len && c > best_c)) {
+                        best_len = len;
+                        best_c = c;
+                    }
+                };
+                for (uint32_t d = 8; d <= 64; d += 8)
+                    if (p >= d) probe(p - d);
+                const uint32_t h = H[snappy_hash(w)];
+                if (h && p - (h - 1) <= SNAPPY_MAX_OFFSET) probe(h - 1);
+            }
+            const unsigned long long m8 = __ballot(best_len >= 8);
+            const unsigned long long many = __ballot(best_len > 0);
+            const unsigned long long sel = m8 ? m8 : many;
+            uint32_t ins_end = end;
+            if (sel) {
+                const int fl = __ffsll(sel) - 1;
+                const uint32_t first = pos + (uint32_t)fl;
+                const uint32_t c = __shfl(best_c, fl);
+                // full common prefix of src[first..] and src[c..], up to N
+                uint32_t L = 4;
+                for (;;) {
+                    const uint32_t q = first + L + lane;   // c + L + lane < q
+                    const bool stop = q >= N || src[c + L + lane] != src[q];
+                    const unsigned long long sm = __ballot(stop);
+                    if (sm) {
+                        L += (uint32_t)(__ffsll(sm) - 1);
+                        break;
+                    }
+                    L += 64;
+                }
+                if (first > lit_start) emit_literal(lit_start, first);
+                // copies of 64 while L >= 68 (one 3-byte element per lane and
+                // round), then the tail as snappy_emit_copy splits it
+                const uint32_t k64 = L >= 68 ? (L - 68) / 64 + 1 : 0;
+                if (!overflow && (uint64_t)o + 3ull * k64 + 6 > cap)
+                    overflow = true;
+                if (!overflow) {
+                    const uint32_t off = first - c;
+                    for (uint32_t i = lane; i < k64; i += 64)
+                        snappy_emit_copy1(dst + o + 3 * i, off, 64);
+                    o += 3 * k64;
+                    uint32_t kk = 0;
+                    if (lane == 0)
+                        kk = snappy_emit_copy(dst + o, off, L - 64 * k64);
+                    o += __shfl(kk, 0);
+                }
+                if (first + L < end) ins_end = first + L;
+                lit_start = first + L;
+            }
+            if (active && p < ins_end) atomicMax(&H[snappy_hash(w)], p + 1);
+            pos = sel ? lit_start : end;
+            __syncthreads();   // inserts land before the next step's lookups
+        }
+        if (!overflow && lit_start < N) emit_literal(lit_start, N);
+        if (overflow) {   // cannot happen with cap at the bound; never write past
+            if (lane == 0) {
+                atomicAdd(err_flag, 1ull);
+                out_len[pg] = 0;
+            }
+            continue;
+        }
+        if (o >= snappy_stored_size(N)) {
+            // the stored form: what hx_snappy_stored_literal recognises
+            __threadfence();   // the stream's stores are ordered before these
+            k = 0;
+            if (lane == 0) k = snappy_emit_varint(dst, N);
+            o = __shfl(k, 0);
+            if (N) emit_literal(0, N);
+        }
+        if (lane == 0) out_len[pg] = o;
+    }
+}
+
+// Scan-and-pack behind kernel 1e, so the host takes the streams in one
+// contiguous copy of sum(out_len) bytes. The scan: ONE block walks out_len in
+// tiles of 256, an inclusive LDS scan per tile and a carry from tile to tile,
+// and writes offs[i] = sum(out_len[0, i)) — linear in the page count.
+__global__ void __launch_bounds__(256)
+k_snappy_scan(const uint32_t* __restrict__ out_len, uint32_t n_pages,
+              unsigned long long* __restrict__ offs) {
+    __shared__ unsigned long long part[256];
+    const uint32_t t = threadIdx.x;
+    unsigned long long carry = 0;
+    for (uint32_t base = 0; base < n_pages; base += 256) {
+        const uint32_t i = base + t;
+        const unsigned long long own = i < n_pages ? out_len[i] : 0;
+        part[t] = own;
+        __syncthreads();
+        for (uint32_t st = 1; st < 256; st <<= 1) {
+            const unsigned long long add = t >= st ? part[t - st] : 0;
+            __syncthreads();
+            part[t] += add;
+            __syncthreads();
+        }
+        if (i < n_pages) offs[i] = carry + part[t] - own;
+        carry += part[255];
+        __syncthreads();   // part[255] read by all before the next tile
+    }
+}
+
+// The pack: one block per page copies its stream from its slot to
+// packed + offs[page].
+__global__ void __launch_bounds__(256)
+k_snappy_pack(const uint8_t* __restrict__ slots,
+              const SnappyCompDesc* __restrict__ pages, uint32_t n_pages,
+              const uint32_t* __restrict__ out_len,
+              const unsigned long long* __restrict__ offs,
+              uint8_t* __restrict__ packed) {
+    for (uint32_t pg = blockIdx.x; pg < n_pages; pg += gridDim.x)
+        sc_copy(packed + offs[pg], slots + pages[pg].dst_off, out_len[pg],
+                threadIdx.x, 256);
+}
+
+// Footer statistics of the pages kernel 1e compresses, so the raw columns
+// need not cross PCIe for them: one wave per page of 8-byte values, min and
+// max through an order-preserving u64 key (u64: the bits; i64: sign flipped;
+// f64: the usual total-order key, NaN skipped). The f64 bounds leave as the
+// writer's minmax_bytes leaves them: a zero bound is min -0.0 / max +0.0.
+__global__ void __launch_bounds__(64)
+k_page_minmax(const uint8_t* __restrict__ src_base,
+              const SnappyCompDesc* __restrict__ pages,
+              const uint32_t* __restrict__ kinds, uint32_t n_pages,
+              PageStat* __restrict__ out) {
+    const uint64_t SIGN = 0x8000000000000000ull;
+    for (uint32_t pg = blockIdx.x; pg < n_pages; pg += gridDim.x) {
+        const SnappyCompDesc pd = pages[pg];
+        const uint32_t kind = kinds[pg];
+        const uint64_t* v = (const uint64_t*)(src_base + pd.src_off);
+        const uint32_t n_vals = pd.n >> 3;
+        unsigned long long lo = ~0ull, hi = 0ull;
+        bool any = false;
+        for (uint32_t i = threadIdx.x; i < n_vals; i += 64) {
+            const uint64_t b = v[i];
+            uint64_t key = b;
+            if (kind == PAGE_ORDER_I64) {
+                key = b ^ SIGN;
+            } else if (kind == PAGE_ORDER_F64) {
+                if ((b & ~SIGN) > 0x7FF0000000000000ull) continue;   // NaN
+                key = (b & SIGN) ? ~b : (b | SIGN);
+            }
+            any = true;
+            lo = key < lo ? key : lo;
+            hi = key > hi ? key : hi;
+        }
+        for (int m = 32; m > 0; m >>= 1) {
+            const unsigned long long l2 = __shfl_xor(lo, m);
+            const unsigned long long h2 = __shfl_xor(hi, m);
+            lo = l2 < lo ? l2 : lo;
+            hi = h2 > hi ? h2 : hi;
+        }
+        const bool has = __ballot(any) != 0;
+        if (threadIdx.x == 0) {
+            uint64_t mn = lo, mx = hi;
+            if (kind == PAGE_ORDER_I64) {
+                mn ^= SIGN;
+                mx ^= SIGN;
+            } else if (kind == PAGE_ORDER_F64) {
+                mn = (mn & SIGN) ? (mn & ~SIGN) : ~mn;
+                mx = (mx & SIGN) ? (mx & ~SIGN) : ~mx;
+                if ((mn & ~SIGN) == 0) mn = SIGN;   // -0.0
+                if ((mx & ~SIGN) == 0) mx = 0;      // +0.0
+            }
+            out[pg] = PageStat{has ? mn : 0, has ? mx : 0, has ? 1ull : 0ull};
+        }
+    }
+}
+
 static uint32_t grid_for(uint32_t work, uint32_t per_block) {
     uint32_t g = (work + per_block - 1) / per_block;
     return g == 0 ? 1 : (g > 2048u ? 2048u : g);
@@ -2806,6 +3116,42 @@ hipError_t launch_snappy(hipStream_t s, const uint8_t* blob, uint8_t* dec,
     else
         hipLaunchKernelGGL(k_snappy_decompress<1>, dim3(blocks), dim3(256),
                            0, s, blob, dec, pages, n_pages, err_flag);
+    return hipGetLastError();
+}
+
+hipError_t launch_snappy_compress(hipStream_t s, const uint8_t* src,
+                                  uint8_t* dst, const SnappyCompDesc* pages,
+                                  uint32_t n_pages, uint32_t* out_len,
+                                  unsigned long long* err_flag) {
+    if (n_pages == 0) return hipSuccess;
+    // one wave per page, 16 KB of LDS each: 10 blocks fit a CU
+    const uint32_t grid = n_pages > 65536u ? 65536u : n_pages;
+    hipLaunchKernelGGL(k_snappy_compress, dim3(grid), dim3(64), 0, s, src,
+                       dst, pages, n_pages, out_len, err_flag);
+    return hipGetLastError();
+}
+
+hipError_t launch_page_minmax(hipStream_t s, const uint8_t* src,
+                              const SnappyCompDesc* pages,
+                              const uint32_t* kinds, uint32_t n_pages,
+                              PageStat* out) {
+    if (n_pages == 0) return hipSuccess;
+    const uint32_t grid = n_pages > 65536u ? 65536u : n_pages;
+    hipLaunchKernelGGL(k_page_minmax, dim3(grid), dim3(64), 0, s, src, pages,
+                       kinds, n_pages, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_snappy_pack(hipStream_t s, const uint8_t* slots,
+                              const SnappyCompDesc* pages, uint32_t n_pages,
+                              const uint32_t* out_len,
+                              unsigned long long* offs, uint8_t* packed) {
+    if (n_pages == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_snappy_scan, dim3(1), dim3(256), 0, s, out_len,
+                       n_pages, offs);
+    const uint32_t grid = n_pages > 65536u ? 65536u : n_pages;
+    hipLaunchKernelGGL(k_snappy_pack, dim3(grid), dim3(256), 0, s, slots,
+                       pages, n_pages, out_len, offs, packed);
     return hipGetLastError();
 }
 

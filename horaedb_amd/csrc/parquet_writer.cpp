@@ -3,6 +3,7 @@
 // of thrift_compact.h's reader).
 #include "parquet_writer.h"
 #include "def_levels.h"
+#include "snappy_compress.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -92,7 +93,9 @@ void statistics(TW& w, const std::string& mn, const std::string& mx) {
 
 struct ChunkMeta {
     int64_t data_page_offset;
-    int64_t total_size;
+    int64_t total_size;             // page header + uncompressed payload
+    int64_t total_compressed = 0;   // page header + payload as written
+    int32_t codec = 0;              // 0 UNCOMPRESSED, 1 SNAPPY
     int64_t num_values;
     std::string mn, mx;
     bool has_stats = true;
@@ -133,10 +136,10 @@ void column_chunk(TW& w, const char* name, int32_t physical,
         w.varint(strlen(name));
         w.buf.insert(w.buf.end(), (const uint8_t*)name,
                      (const uint8_t*)name + strlen(name));
-        w.i32(l2, 4, 0);                               // codec UNCOMPRESSED
+        w.i32(l2, 4, m.codec);                         // UNCOMPRESSED / SNAPPY
         w.i64f(l2, 5, m.num_values);
         w.i64f(l2, 6, m.total_size);                   // uncompressed
-        w.i64f(l2, 7, m.total_size);                   // compressed
+        w.i64f(l2, 7, m.total_compressed);             // compressed
         w.i64f(l2, 9, m.data_page_offset);
         if (m.optional) {
             w.field(l2, 12, 12);                       // statistics
@@ -150,12 +153,13 @@ void column_chunk(TW& w, const char* name, int32_t physical,
     w.stop();
 }
 
-std::vector<uint8_t> page_header(int32_t n_values, int32_t payload) {
+std::vector<uint8_t> page_header(int32_t n_values, int32_t payload,
+                                 int32_t compressed) {
     TW w;
     int16_t last = 0;
-    w.i32(last, 1, 0);        // type DATA_PAGE
-    w.i32(last, 2, payload);  // uncompressed_page_size
-    w.i32(last, 3, payload);  // compressed_page_size
+    w.i32(last, 1, 0);           // type DATA_PAGE
+    w.i32(last, 2, payload);     // uncompressed_page_size
+    w.i32(last, 3, compressed);  // compressed_page_size
     w.field(last, 5, 12);     // data_page_header
     {
         int16_t l2 = 0;
@@ -207,6 +211,94 @@ bool minmax_bytes(const double* v, int64_t n, std::string& mn,
     mn.assign((const char*)&lo, 8);
     mx.assign((const char*)&hi, 8);
     return true;
+}
+
+// Writes one data page: header, then the payload as the codec leaves it. The
+// uncompressed payload is head (a level block, may be empty) followed by
+// body. Under Snappy the payload is `ready` when the caller brought one, else
+// the host twin's stream of {head, body}; both are the same bytes. A page
+// equal to the column's previous page reuses that page's stream (full pages
+// of a constant __seq__, __reserved__ zeros).
+struct PageWriter {
+    int32_t codec;
+    const PagePayload* ready;   // [row group * n_cols + column], or null
+    int32_t n_cols;
+    struct Prev {
+        std::vector<uint8_t> raw, comp;
+        bool valid = false;
+    };
+    std::vector<Prev> prev;
+    std::vector<uint8_t> joined;
+    PageWriter(int32_t codec_, const PagePayload* ready_, int32_t n_cols_)
+        : codec(codec_), ready(ready_), n_cols(n_cols_), prev(n_cols_) {}
+
+    // false on a failed write; m gets sizes, codec and data_page_offset
+    bool write(FILE* f, int64_t g, int32_t c, bool compressible,
+               int32_t n_values, const uint8_t* head, size_t head_len,
+               const uint8_t* body, size_t body_len, int64_t& off,
+               ChunkMeta& m) {
+        const size_t payload = head_len + body_len;
+        const uint8_t* out = nullptr;
+        size_t out_len = payload;
+        const bool snappy = codec == 1 && compressible;
+        if (snappy) {
+            const PagePayload* r = ready ? &ready[g * n_cols + c] : nullptr;
+            if (r && r->ptr) {
+                out = r->ptr;
+                out_len = r->len;
+            } else {
+                const uint8_t* raw = body;
+                if (head_len) {
+                    joined.assign(head, head + head_len);
+                    joined.insert(joined.end(), body, body + body_len);
+                    raw = joined.data();
+                }
+                Prev& pv = prev[c];
+                if (!pv.valid || pv.raw.size() != payload ||
+                    (payload && std::memcmp(pv.raw.data(), raw, payload))) {
+                    pv.raw.assign(raw, raw + payload);
+                    pv.comp.resize(size_t(snappy_max_compressed(payload)));
+                    pv.comp.resize(snappy_compress_host(
+                        raw, payload, pv.comp.data(), pv.comp.size()));
+                    pv.valid = true;
+                }
+                out = pv.comp.data();
+                out_len = pv.comp.size();
+            }
+        }
+        auto hdr = page_header(n_values, int32_t(payload), int32_t(out_len));
+        m.data_page_offset = off;
+        m.codec = snappy ? 1 : 0;
+        m.total_size = int64_t(hdr.size() + payload);
+        m.total_compressed = int64_t(hdr.size() + out_len);
+        if (fwrite(hdr.data(), 1, hdr.size(), f) != hdr.size()) return false;
+        if (snappy) {
+            if (out_len && fwrite(out, 1, out_len, f) != out_len) return false;
+        } else {
+            if (head_len && fwrite(head, 1, head_len, f) != head_len)
+                return false;
+            if (body_len && fwrite(body, 1, body_len, f) != body_len)
+                return false;
+        }
+        off += m.total_compressed;
+        return true;
+    }
+};
+
+// Statistics a ready page brought along; false = compute from the column.
+bool stats_from_ready(const PagePayload* ready, int64_t idx, ChunkMeta& m) {
+    if (!ready || !ready[idx].ptr || ready[idx].stats == 0) return false;
+    m.has_stats = ready[idx].stats == 1;
+    m.mn.assign((const char*)&ready[idx].min_bits, 8);
+    m.mx.assign((const char*)&ready[idx].max_bits, 8);
+    return true;
+}
+
+// A column given as a null pointer needs every page ready with statistics.
+bool column_present(const void* data, const PagePayload* ready, int64_t idx,
+                    int32_t codec) {
+    return data || (codec == 1 && ready && ready[idx].ptr &&
+                    ready[idx].stats != 0);
 }
 
 struct MetricRG {
@@ -263,8 +355,10 @@ bool metric_footer(FILE* f, const std::vector<MetricRG>& rgs, int64_t n,
 
 std::string write_metric_sst(const std::string& path, const uint64_t* series,
                              const int64_t* ts, const double* value,
-                             uint64_t seq, int64_t n, int64_t row_group) {
+                             uint64_t seq, int64_t n, int64_t row_group,
+                             int32_t codec, const PagePayload* ready) {
     if (n <= 0) return "write_metric_sst: no rows";
+    if (codec != 0 && codec != 1) return "write_metric_sst: unknown codec";
     FILE* f = fopen(path.c_str(), "wb");
     if (!f) return "write_metric_sst: cannot open " + path;
     auto fail = [&](const char* m) {
@@ -278,24 +372,25 @@ std::string write_metric_sst(const std::string& path, const uint64_t* series,
     std::vector<uint64_t> seq_col;   // constant per file (closure precondition)
     std::vector<uint64_t> zeros;
     std::vector<MetricRG> rgs;
-    for (int64_t base = 0; base < n; base += row_group) {
+    PageWriter pw(codec, ready, 5);
+    for (int64_t g = 0, base = 0; base < n; g++, base += row_group) {
         int64_t rows = std::min<int64_t>(row_group, n - base);
         if ((int64_t)seq_col.size() < rows) {
             seq_col.assign(rows, seq);
             zeros.assign(rows, 0);
         }
-        const void* data[5] = {series + base, ts + base, value + base,
+        const void* data[5] = {series ? series + base : nullptr,
+                               ts ? ts + base : nullptr,
+                               value ? value + base : nullptr,
                                seq_col.data(), zeros.data()};
         MetricRG rg;
         rg.num_rows = rows;
         for (int c = 0; c < 5; c++) {
-            int32_t payload = int32_t(rows * 8);
-            auto hdr = page_header((int32_t)rows, payload);
             ChunkMeta& m = rg.cols[c];
-            m.data_page_offset = off;
             m.num_values = rows;
-            m.total_size = int64_t(hdr.size()) + payload;
-            switch (c) {
+            if (!column_present(data[c], ready, g * 5 + c, codec))
+                return fail("write_metric_sst: column neither given nor ready");
+            if (!stats_from_ready(ready, g * 5 + c, m)) switch (c) {
                 case 0: case 3: case 4:
                     minmax_bytes((const uint64_t*)data[c], rows, m.mn, m.mx);
                     break;
@@ -307,11 +402,9 @@ std::string write_metric_sst(const std::string& path, const uint64_t* series,
                                                m.mn, m.mx);
                     break;
             }
-            if (fwrite(hdr.data(), 1, hdr.size(), f) != hdr.size())
+            if (!pw.write(f, g, c, true, (int32_t)rows, nullptr, 0,
+                          (const uint8_t*)data[c], size_t(rows) * 8, off, m))
                 return fail("write failed");
-            if (fwrite(data[c], 8, rows, f) != size_t(rows))
-                return fail("write failed");
-            off += m.total_size;
         }
         rgs.push_back(rg);
     }
@@ -326,8 +419,12 @@ std::string write_metric_sst_nullable(const std::string& path,
                                       const int64_t* ts,
                                       const NullableValues& value,
                                       const uint64_t* seqs, uint64_t seq,
-                                      int64_t n, int64_t row_group) {
+                                      int64_t n, int64_t row_group,
+                                      int32_t codec,
+                                      const PagePayload* ready) {
     if (n <= 0) return "write_metric_sst_nullable: no rows";
+    if (codec != 0 && codec != 1)
+        return "write_metric_sst_nullable: unknown codec";
     if (row_group <= 0 || row_group % 64)
         return "write_metric_sst_nullable: row_group is not a multiple of 64";
     const int64_t wpg = row_group / 64;
@@ -347,6 +444,7 @@ std::string write_metric_sst_nullable(const std::string& path,
     std::vector<uint64_t> seq_col, zeros;
     std::vector<uint8_t> levels;
     std::vector<MetricRG> rgs;
+    PageWriter pw(codec, ready, 5);
     for (int64_t g = 0, base = 0; base < n; g++, base += row_group) {
         const int64_t rows = std::min<int64_t>(row_group, n - base);
         if (!seqs && (int64_t)seq_col.size() < rows) seq_col.assign(rows, seq);
@@ -356,21 +454,24 @@ std::string write_metric_sst_nullable(const std::string& path,
         levels.clear();
         encode_def_levels(value.bitmap_words + g * wpg, (uint32_t)rows,
                           (uint32_t)nv, levels);
-        const void* data[5] = {series + base, ts + base, packed,
+        const void* data[5] = {series ? series + base : nullptr,
+                               ts ? ts + base : nullptr, packed,
                                seqs ? seqs + base : seq_col.data(),
                                zeros.data()};
         MetricRG rg;
         rg.num_rows = rows;
         for (int c = 0; c < 5; c++) {
             const int64_t body = (c == 2 ? nv : rows) * 8;
-            const int32_t payload =
-                int32_t(body + (c == 2 ? (int64_t)levels.size() : 0));
-            auto hdr = page_header((int32_t)rows, payload);
             ChunkMeta& m = rg.cols[c];
-            m.data_page_offset = off;
             m.num_values = rows;
-            m.total_size = int64_t(hdr.size()) + payload;
-            switch (c) {
+            if (!column_present(data[c], ready, g * 5 + c, codec))
+                return fail("write_metric_sst_nullable: column neither given "
+                            "nor ready");
+            if (c == 2) {
+                m.optional = true;
+                m.null_count = rows - nv;
+            }
+            if (!stats_from_ready(ready, g * 5 + c, m)) switch (c) {
                 case 0: case 3: case 4:
                     minmax_bytes((const uint64_t*)data[c], rows, m.mn, m.mx);
                     break;
@@ -378,20 +479,14 @@ std::string write_metric_sst_nullable(const std::string& path,
                     minmax_bytes((const int64_t*)data[c], rows, m.mn, m.mx);
                     break;
                 case 2:
-                    m.optional = true;
-                    m.null_count = rows - nv;
                     m.has_stats = minmax_bytes((const double*)data[c], nv,
                                                m.mn, m.mx);
                     break;
             }
-            if (fwrite(hdr.data(), 1, hdr.size(), f) != hdr.size())
+            if (!pw.write(f, g, c, true, (int32_t)rows, levels.data(),
+                          c == 2 ? levels.size() : 0,
+                          (const uint8_t*)data[c], size_t(body), off, m))
                 return fail("write failed");
-            if (c == 2 && fwrite(levels.data(), 1, levels.size(), f) !=
-                              levels.size())
-                return fail("write failed");
-            if (body && fwrite(data[c], 1, size_t(body), f) != size_t(body))
-                return fail("write failed");
-            off += m.total_size;
         }
         rgs.push_back(rg);
     }
@@ -408,8 +503,10 @@ std::string write_metric_sst_nullable(const std::string& path,
 // byte values longer than 64 B), thrift-compact footer with column_orders.
 // ---------------------------------------------------------------------------
 std::string write_table_sst(const std::string& path, const WriterCol* cols,
-                            int32_t n_cols, int64_t n, int64_t row_group) {
+                            int32_t n_cols, int64_t n, int64_t row_group,
+                            int32_t codec, const PagePayload* ready) {
     if (n <= 0 || n_cols <= 0) return "write_table_sst: no rows/cols";
+    if (codec != 0 && codec != 1) return "write_table_sst: unknown codec";
     FILE* f = fopen(path.c_str(), "wb");
     if (!f) return "write_table_sst: cannot open " + path;
     auto fail = [&](const char* m) {
@@ -433,7 +530,8 @@ std::string write_table_sst(const std::string& path, const WriterCol* cols,
     };
     std::vector<RG> rgs;
     std::vector<uint8_t> payload;
-    for (int64_t base = 0; base < n; base += row_group) {
+    PageWriter pw(codec, ready, n_cols);
+    for (int64_t g = 0, base = 0; base < n; g++, base += row_group) {
         int64_t rows = std::min<int64_t>(row_group, n - base);
         RG rg;
         rg.num_rows = rows;
@@ -442,7 +540,6 @@ std::string write_table_sst(const std::string& path, const WriterCol* cols,
             const WriterCol& wc = cols[c];
             ChunkMeta& m = rg.cols[c];
             m.num_values = rows;
-            m.data_page_offset = off;
             const uint8_t* body = nullptr;
             size_t body_len = 0;
             if (wc.physical == 6) {
@@ -467,9 +564,14 @@ std::string write_table_sst(const std::string& path, const WriterCol* cols,
                 body = payload.data();
                 body_len = payload.size();
             } else {
-                body = (const uint8_t*)wc.data + base * 8;
+                if (!column_present(wc.data, ready, g * n_cols + c, codec))
+                    return fail("write_table_sst: column neither given nor "
+                                "ready");
+                body = wc.data ? (const uint8_t*)wc.data + base * 8 : nullptr;
                 body_len = size_t(rows) * 8;
-                if (wc.physical == 5)
+                if (stats_from_ready(ready, g * n_cols + c, m)) {
+                    // the ready page brought them
+                } else if (wc.physical == 5)
                     m.has_stats = minmax_bytes((const double*)wc.data + base,
                                                rows, m.mn, m.mx);
                 else if (wc.converted == 14)
@@ -479,14 +581,10 @@ std::string write_table_sst(const std::string& path, const WriterCol* cols,
                     minmax_bytes((const int64_t*)wc.data + base, rows, m.mn,
                                  m.mx);
             }
-            auto hdr = page_header((int32_t)rows, (int32_t)body_len);
-            m.total_size = int64_t(hdr.size()) + int64_t(body_len);
-            if (fwrite(hdr.data(), 1, hdr.size(), f) != hdr.size())
+            // BYTE_ARRAY chunks stay uncompressed under every codec
+            if (!pw.write(f, g, c, wc.physical != 6, (int32_t)rows, nullptr,
+                          0, body, body_len, off, m))
                 return fail("write failed");
-            if (body_len &&
-                fwrite(body, 1, body_len, f) != body_len)
-                return fail("write failed");
-            off += m.total_size;
         }
         rgs.push_back(std::move(rg));
     }
@@ -544,7 +642,8 @@ std::string write_table_sst(const std::string& path, const WriterCol* cols,
 std::string write_metric_sst_seqs(const std::string& path,
                                   const uint64_t* series, const int64_t* ts,
                                   const double* value, const uint64_t* seqs,
-                                  int64_t n, int64_t row_group) {
+                                  int64_t n, int64_t row_group,
+                                  int32_t codec, const PagePayload* ready) {
     std::vector<uint64_t> zeros(n, 0);
     WriterCol cols[5] = {
         {"series_id", 2, 14, series, nullptr},
@@ -553,7 +652,7 @@ std::string write_metric_sst_seqs(const std::string& path,
         {"__seq__", 2, 14, seqs, nullptr},
         {"__reserved__", 2, 14, zeros.data(), nullptr},
     };
-    return write_table_sst(path, cols, 5, n, row_group);
+    return write_table_sst(path, cols, 5, n, row_group, codec, ready);
 }
 
 }  // namespace hx

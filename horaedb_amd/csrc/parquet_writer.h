@@ -2,8 +2,9 @@
 // (DESIGN.md §10 / SURVEY §8(f) row 1). Writes exactly the reference writer's
 // metric-SST layout (storage.rs:193-298 contract): 5 flat REQUIRED columns
 // (series_id u64, timestamp i64, value f64, __seq__ u64, __reserved__ u64),
-// row groups of `row_group` rows, one PLAIN uncompressed data page v1 per
-// chunk, min/max statistics, thrift-compact footer. Readable by parquet-rs /
+// row groups of `row_group` rows, one PLAIN data page v1 per chunk
+// (uncompressed, or Snappy as the reference's default config writes them),
+// min/max statistics, thrift-compact footer. Readable by parquet-rs /
 // pyarrow (validated in tests) and by our own reader.
 #pragma once
 #include <cstdint>
@@ -11,12 +12,36 @@
 
 namespace hx {
 
+// Codec of the 8-byte columns' pages: 0 = UNCOMPRESSED (the default; the file
+// is what it always was), 1 = SNAPPY. Under Snappy every page payload is the
+// stream hx::snappy_compress_host (snappy_compress.h) gives for the page's
+// uncompressed bytes — for an OPTIONAL value page {level block, packed
+// values}, the level block inside the stream. `ready` optionally brings
+// streams made elsewhere (kernel 1e): entry [row group * n_cols + column],
+// ptr null = absent, the writer compresses that page itself. A ready stream
+// must be the twin's bytes for the page, so the file does not depend on who
+// compressed it. BYTE_ARRAY chunks stay uncompressed.
+// A ready entry may bring the chunk's statistics too (k_page_minmax, the raw
+// 8 bytes of min and max as minmax over the column would give them); a
+// column whose every page comes ready WITH statistics may be passed as a
+// null pointer — its rows never reach the host.
+struct PagePayload {
+    const uint8_t* ptr;
+    uint32_t len;
+    uint32_t stats;      // 0: the writer computes them from the column;
+                         // 1: min_bits / max_bits; 2: the chunk has none
+    uint64_t min_bits;
+    uint64_t max_bits;
+};
+
 // columns are caller-provided arrays of n rows; seq is constant per file
 // (the compacted file's sequence — see hx_compact's closure precondition).
 // Returns empty string on success, else an error message.
 std::string write_metric_sst(const std::string& path, const uint64_t* series,
                              const int64_t* ts, const double* value,
-                             uint64_t seq, int64_t n, int64_t row_group);
+                             uint64_t seq, int64_t n, int64_t row_group,
+                             int32_t codec = 0,
+                             const PagePayload* ready = nullptr);
 
 // Nullable form of the metric writer: the `value` column is declared OPTIONAL
 // (the reference's shape for it), the four others stay REQUIRED. The values
@@ -41,7 +66,9 @@ std::string write_metric_sst_nullable(const std::string& path,
                                       const int64_t* ts,
                                       const NullableValues& value,
                                       const uint64_t* seqs, uint64_t seq,
-                                      int64_t n, int64_t row_group);
+                                      int64_t n, int64_t row_group,
+                                      int32_t codec = 0,
+                                      const PagePayload* ready = nullptr);
 
 // General flat-table writer (same page/footer layout) for the auxiliary
 // tables the RFC defines (metrics/series/tags/index,
@@ -57,13 +84,17 @@ struct WriterCol {
 };
 
 std::string write_table_sst(const std::string& path, const WriterCol* cols,
-                            int32_t n_cols, int64_t n, int64_t row_group);
+                            int32_t n_cols, int64_t n, int64_t row_group,
+                            int32_t codec = 0,
+                            const PagePayload* ready = nullptr);
 
 // per-row variable-length seq variant of the metric writer (general
 // compaction outputs, executor.rs:155-222 keep_builtin path)
 std::string write_metric_sst_seqs(const std::string& path,
                                   const uint64_t* series, const int64_t* ts,
                                   const double* value, const uint64_t* seqs,
-                                  int64_t n, int64_t row_group);
+                                  int64_t n, int64_t row_group,
+                                  int32_t codec = 0,
+                                  const PagePayload* ready = nullptr);
 
 }  // namespace hx

@@ -123,6 +123,18 @@ def _load():
         C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int64),
         C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.c_uint64, C.c_int64,
         C.c_int64]
+    lib.hx_set_write_codec.argtypes = [C.c_void_p, C.c_int32]
+    lib.hx_write_sst_codec.argtypes = [
+        C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int64),
+        C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.c_int32, C.c_uint64,
+        C.c_int64, C.c_int64, C.c_int32]
+    lib.hx_debug_snappy_compress_host.argtypes = [
+        C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]
+    lib.hx_debug_snappy_compress_host.restype = C.c_uint64
+    lib.hx_debug_snappy_compress.argtypes = [
+        C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.c_uint32,
+        C.POINTER(C.c_uint32), C.c_void_p, C.POINTER(C.c_uint64),
+        C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
     lib.hx_debug_pack_optional.argtypes = [
         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint8),
         C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32,
@@ -440,6 +452,13 @@ class Store:
         write(valid=...), compact and compact_files."""
         _check(_lib.hx_set_nullable_values(self._h, 1 if on else 0))
 
+    def set_write_codec(self, codec):
+        """Writer setting (hx_set_write_codec): CODEC_NONE (default) or
+        CODEC_SNAPPY, the page codec of every SST this store writes from now
+        on (write, compact, compact_files); combines with
+        set_nullable_values."""
+        _check(_lib.hx_set_write_codec(self._h, int(codec)))
+
     def write(self, series, ts, value, enable_check=True, valid=None):
         """ColumnarStorage::write (storage.rs:76-89): stable PK sort + new
         SST + catalog add. Returns the new file's sequence. valid: bool
@@ -604,6 +623,87 @@ def write_sst_native_nullable(path, series, ts, value, seq, valid=None,
         value.ctypes.data_as(C.POINTER(C.c_double)),
         None if bits is None else bits.ctypes.data_as(C.POINTER(C.c_uint8)),
         seq, n, row_group))
+
+
+CODEC_NONE, CODEC_SNAPPY = 0, 1
+
+
+def write_sst_native_codec(path, series, ts, value, seq, codec, valid=None,
+                           nullable=False, row_group=8192):
+    """GPU-free writer with a page codec (hx_write_sst_codec). nullable
+    declares `value` OPTIONAL (valid: bool array, False = null, or None);
+    without it valid must be None."""
+    series = np.ascontiguousarray(series, dtype=np.uint64)
+    ts = np.ascontiguousarray(ts, dtype=np.int64)
+    value = np.ascontiguousarray(value, dtype=np.float64)
+    n = len(series)
+    bits = None if valid is None else _validity_bits(valid, n)
+    _check(_lib.hx_write_sst_codec(
+        path.encode(), series.ctypes.data_as(C.POINTER(C.c_uint64)),
+        ts.ctypes.data_as(C.POINTER(C.c_int64)),
+        value.ctypes.data_as(C.POINTER(C.c_double)),
+        None if bits is None else bits.ctypes.data_as(C.POINTER(C.c_uint8)),
+        1 if nullable else 0, seq, n, row_group, int(codec)))
+
+
+def snappy_max_compressed(n):
+    """Snappy's bound on the stream of an n-byte page; a smaller output slot
+    is refused by the host twin and by kernel 1e."""
+    return 32 + n + n // 6
+
+
+def snappy_compress_host(page, cap=None):
+    """The host twin of kernel 1e (test hook hx_debug_snappy_compress_host;
+    no GPU needed): the Snappy stream of `page` (bytes-like) as bytes, or
+    None when cap (default: the bound) is refused."""
+    src = np.frombuffer(bytes(page), dtype=np.uint8)
+    n = len(src)
+    cap = snappy_max_compressed(n) if cap is None else cap
+    dst = np.full(max(cap, 1), 0xA5, dtype=np.uint8)
+    size = _lib.hx_debug_snappy_compress_host(
+        src.ctypes.data if n else None, n, dst.ctypes.data, cap)
+    if size == 0:
+        if (dst != 0xA5).any():
+            raise RuntimeError("refused call wrote to dst")
+        return None
+    return dst[:size].tobytes()
+
+
+def snappy_compress_device(pages, src_align=None, caps=None):
+    """Kernel 1e through the test hook hx_debug_snappy_compress (needs a GPU):
+    one production launch over `pages` (a list of bytes). src_align: byte
+    misalignment 0..63 per page (default 0); caps: output slot size per page
+    (default: the bound). Returns (streams, slots, n_errors): streams[i] is
+    the page's stream, None for a refused page; slots[i] is its whole output
+    slot as the device left it (pre-filled with 0xEE)."""
+    n = len(pages)
+    lens = np.array([len(p) for p in pages], dtype=np.uint32)
+    offs = np.zeros(n, dtype=np.uint64)
+    if n:
+        offs[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+    blob = np.frombuffer(b"".join(pages) or b"\0", dtype=np.uint8)
+    align = np.zeros(n, dtype=np.uint32) if src_align is None else \
+        np.ascontiguousarray(src_align, dtype=np.uint32)
+    if caps is None:
+        caps = [snappy_max_compressed(int(x)) for x in lens]
+    out_offs = np.zeros(n + 1, dtype=np.uint64)
+    out_offs[1:] = np.cumsum(np.asarray(caps, dtype=np.uint64))
+    out = np.zeros(max(int(out_offs[-1]), 1), dtype=np.uint8)
+    out_lens = np.zeros(max(n, 1), dtype=np.uint32)
+    errs = C.c_uint64()
+    _check(_lib.hx_debug_snappy_compress(
+        blob.ctypes.data, offs.ctypes.data_as(C.POINTER(C.c_uint64)),
+        lens.ctypes.data_as(C.POINTER(C.c_uint32)), n,
+        align.ctypes.data_as(C.POINTER(C.c_uint32)), out.ctypes.data,
+        out_offs.ctypes.data_as(C.POINTER(C.c_uint64)),
+        out_lens.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(errs)))
+    streams, slots = [], []
+    for i in range(n):
+        a, b = int(out_offs[i]), int(out_offs[i + 1])
+        slots.append(out[a:b].tobytes())
+        streams.append(out[a:a + int(out_lens[i])].tobytes()
+                       if out_lens[i] else None)
+    return streams, slots, errs.value
 
 
 def pack_optional(values, n, row_group, valid_words=None, valid_bits=None,

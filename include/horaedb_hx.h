@@ -40,7 +40,9 @@ enum {
                                 under Append mode; null values reaching the
                                 write side (compaction inputs, a zero bit
                                 given to hx_write_nullable) of a handle
-                                that has not set hx_set_nullable_values   */
+                                that has not set hx_set_nullable_values;
+                                hx_set_write_codec on a store with a
+                                Binary value column                       */
     HX_ERR_NO_GPU     = 4,   /* HIP runtime/device unavailable */
     HX_ERR_HIP        = 5,   /* HIP call failed (see hx_last_error) */
     HX_ERR_INVALID    = 6,   /* bad argument */
@@ -316,6 +318,33 @@ hx_status hx_write_sst_nullable(const char* path, const uint64_t* series,
 hx_status hx_write_sst(const char* path, const uint64_t* series,
                        const int64_t* ts, const double* value, uint64_t seq,
                        int64_t n_rows, int64_t row_group);
+
+/* Page codec of the SSTs this library writes. SNAPPY is the reference's
+ * default on-disk form (PLAIN pages, Snappy-compressed, config.rs:120-133);
+ * all five columns are compressed, an OPTIONAL value page with its level
+ * block inside the stream. The bytes of a compressed page are a function of
+ * the page bytes alone, whichever route (device ingest or compaction, host
+ * ingest, hx_write_sst_codec) wrote the file. */
+enum { HX_CODEC_NONE = 0, HX_CODEC_SNAPPY = 1 };
+
+/* Writer setting, per handle like hx_set_nullable_values; default
+ * HX_CODEC_NONE (nothing changes). From then on every SST the handle writes
+ * (hx_write, hx_write_nullable, hx_compact, hx_compact_files) carries pages
+ * of that codec; it combines freely with hx_set_nullable_values. An unknown
+ * codec returns HX_ERR_INVALID; HX_CODEC_SNAPPY on a store with a Binary
+ * value column returns HX_ERR_UNSUPPORTED (HX_CODEC_NONE changes nothing
+ * and is accepted, as hx_set_nullable_values(h, 0) is). */
+hx_status hx_set_write_codec(hx_handle*, int32_t codec);
+
+/* GPU-free writer with a codec; nullable = 1 declares value OPTIONAL
+ * (validity as for hx_write_sst_nullable), nullable = 0 requires validity
+ * NULL. Codec 0 writes the file hx_write_sst / hx_write_sst_nullable write,
+ * byte for byte. */
+hx_status hx_write_sst_codec(const char* path, const uint64_t* series,
+                             const int64_t* ts, const double* value,
+                             const uint8_t* validity, int32_t nullable,
+                             uint64_t seq, int64_t n_rows, int64_t row_group,
+                             int32_t codec);
 
 /* ---- inverted index (RFC docs/rfcs/20240827-metric-engine.md:86-137) ----
  * The reference's planned index tables (its metric_engine index module is
