@@ -1,0 +1,140 @@
+// ba_pages.h — host twin of kernel 1f (k_ba_page_sizes / k_ba_build_pages in
+// kernels.hip): the PLAIN BYTE_ARRAY page images of a Binary
+// `value` column, built from per-row handles. No GPU header is included; the
+// stand-alone check (ba_pages_check.cpp) compiles this file with a host
+// compiler under ASan/UBSan.
+//
+// A handle is what k_ba_offsets leaves per row: (offset << 20) | length, the
+// offset relative to a source base of src_size bytes. The 20 length bits are
+// the limit every writer of this library enforces: no value, and no Append
+// concatenation, of 2^20 bytes or more is ever written, because the reader
+// could not describe it.
+//
+// Output row i is source row i, or with group_start (n_out + 1 entries) the
+// concatenation of source rows [group_start[i], group_start[i + 1]) in that
+// order under ONE length prefix (BytesMergeOperator::merge). The page of
+// output row group g (rows [g * R, min(n_out, (g + 1) * R))) is, per row,
+// u32 length little-endian followed by the bytes, back to back; page g starts
+// at page_off[g] of one contiguous image of page_off[n_pages] bytes.
+//
+// The two passes and their rules are the kernels', statement by statement:
+//   sizes  row_len[i] = the row's byte count, or BA_ROW_SKIP when the row is
+//          refused: a group_start pair that decreases or passes n_src (one
+//          error per pair), a handle that does not fit the source (one error
+//          per such HANDLE, so a group with k of them counts k), or a
+//          concatenation above BA_MAX_VALUE_LEN (one over-cap row; not
+//          counted for a row already refused for a handle). A
+//          refused row is written as an empty value and none of its handles
+//          is followed.
+//   build  a page above BA_MAX_PAGE_BYTES is left unwritten (the caller has
+//          refused it from page_off before it gets here).
+#pragma once
+#include <cstdint>
+#include <cstring>
+
+namespace hx {
+
+constexpr uint32_t BA_LEN_BITS = 20;
+constexpr uint32_t BA_LEN_MASK = (1u << BA_LEN_BITS) - 1u;
+// the longest value a handle can describe: 2^20 - 1 bytes
+constexpr uint32_t BA_MAX_VALUE_LEN = BA_LEN_MASK;
+// Parquet's page sizes are i32, and so is BaPageDesc::src_len's use of them
+constexpr uint64_t BA_MAX_PAGE_BYTES = 0x7FFFFFFFull;
+constexpr uint32_t BA_ROW_SKIP = 0x80000000u;
+// rows per row group the build pass can hold offsets for (32 KB of LDS)
+constexpr uint32_t BA_MAX_ROW_GROUP = 8192;
+
+struct BaPagesCounts {
+    uint64_t n_errors;     // bad handles + bad group_start pairs
+    uint64_t n_over_cap;   // rows whose concatenation exceeds BA_MAX_VALUE_LEN
+};
+
+inline uint64_t ba_n_pages(uint64_t n_out, uint64_t R) {
+    return R ? (n_out + R - 1) / R : 0;
+}
+
+// row_len: n_out words; page_off: n_pages + 1 words (exclusive scan of the
+// page sizes, the total last).
+inline BaPagesCounts ba_page_sizes_host(uint64_t src_size,
+                                        const uint64_t* handles,
+                                        uint64_t n_src,
+                                        const uint32_t* group_start,
+                                        uint64_t n_out, uint64_t R,
+                                        uint32_t* row_len,
+                                        uint64_t* page_off) {
+    BaPagesCounts c{0, 0};
+    const uint64_t n_pages = ba_n_pages(n_out, R);
+    uint64_t total = 0;
+    for (uint64_t g = 0; g < n_pages; g++) {
+        page_off[g] = total;
+        const uint64_t r1 = (g + 1) * R < n_out ? (g + 1) * R : n_out;
+        for (uint64_t i = g * R; i < r1; i++) {
+            const uint64_t a = group_start ? group_start[i] : i;
+            const uint64_t b = group_start ? group_start[i + 1] : i + 1;
+            bool skip = false;
+            uint64_t sum = 0;
+            if (a > b || b > n_src) {
+                c.n_errors++;
+                skip = true;
+            } else {
+                for (uint64_t j = a; j < b; j++) {
+                    const uint64_t h = handles[j];
+                    const uint64_t off = h >> BA_LEN_BITS;
+                    const uint64_t len = h & BA_LEN_MASK;
+                    if (off > src_size || len > src_size - off) {
+                        c.n_errors++;
+                        skip = true;
+                    }
+                    sum += len;
+                }
+                if (!skip && sum > BA_MAX_VALUE_LEN) {
+                    c.n_over_cap++;
+                    skip = true;
+                }
+            }
+            row_len[i] = skip ? BA_ROW_SKIP : uint32_t(sum);
+            total += 4 + (skip ? 0 : sum);
+        }
+    }
+    page_off[n_pages] = total;
+    return c;
+}
+
+// out: page_off[n_pages] bytes. Reads nothing outside [src, src + src_size),
+// writes nothing outside a page's own [page_off[g], page_off[g + 1]).
+inline void ba_build_pages_host(const uint8_t* src, uint64_t src_size,
+                                const uint64_t* handles, uint64_t n_src,
+                                const uint32_t* group_start, uint64_t n_out,
+                                uint64_t R, const uint32_t* row_len,
+                                const uint64_t* page_off, uint8_t* out) {
+    const uint64_t n_pages = ba_n_pages(n_out, R);
+    for (uint64_t g = 0; g < n_pages; g++) {
+        if (page_off[g + 1] - page_off[g] > BA_MAX_PAGE_BYTES) continue;
+        uint8_t* p = out + page_off[g];
+        const uint64_t r1 = (g + 1) * R < n_out ? (g + 1) * R : n_out;
+        for (uint64_t i = g * R; i < r1; i++) {
+            const bool skip = (row_len[i] & BA_ROW_SKIP) != 0;
+            const uint32_t len = skip ? 0u : row_len[i];
+            p[0] = uint8_t(len);
+            p[1] = uint8_t(len >> 8);
+            p[2] = uint8_t(len >> 16);
+            p[3] = uint8_t(len >> 24);
+            p += 4;
+            if (skip) continue;
+            const uint64_t a = group_start ? group_start[i] : i;
+            const uint64_t b = group_start ? group_start[i + 1] : i + 1;
+            uint32_t pos = 0;
+            for (uint64_t j = a; j < b && j < n_src; j++) {
+                const uint64_t off = handles[j] >> BA_LEN_BITS;
+                const uint32_t l = uint32_t(handles[j] & BA_LEN_MASK);
+                if (off > src_size || l > src_size - off || l > len - pos)
+                    break;
+                if (l) std::memcpy(p + pos, src + off, l);
+                pos += l;
+            }
+            p += len;
+        }
+    }
+}
+
+}  // namespace hx

@@ -35,6 +35,7 @@
 #include "hx_internal.h"
 #include "stage_chunk.h"
 #include "def_levels.h"
+#include "ba_pages.h"
 
 using hx::align64;
 using hx::ChunkRef;
@@ -1116,7 +1117,10 @@ hx_status ensure_decoded(DevPlan& plan, hipStream_t s) {
     if (decode_err)
         return fail(HX_ERR_FORMAT, "page decode failed (malformed snappy "
                                    "stream, delta page or OPTIONAL page "
-                                   "body)");
+                                   "body; in a Binary value page a bad "
+                                   "length prefix or a value of 2^20 bytes "
+                                   "or more, a value handle has 20 length "
+                                   "bits)");
     plan.decoded = true;
     return HX_OK;
 }
@@ -2672,6 +2676,28 @@ extern "C" uint64_t hx_debug_snappy_compress_host(const uint8_t* src,
     return hx::snappy_compress_host(src, size_t(n), dst, size_t(cap));
 }
 
+// The ingest sort's permutation, shared by hx_write and hx_write_bytes:
+// stable by (series, ts), equal PKs keep input order. Two stable LSD radix
+// passes over a u32 permutation, ts (sign-biased) then series; pc receives
+// the result, d_ka / d_kb / pa / pb are N-entry scratch.
+static hipError_t ingest_sort_perm(hipStream_t s, const uint64_t* d_series,
+                                   const int64_t* d_ts, uint64_t* d_ka,
+                                   uint64_t* d_kb, uint32_t* pa, uint32_t* pb,
+                                   uint32_t* pc, size_t N, void** d_temp,
+                                   size_t* temp_cap) {
+#define SP_TRY(e) do { hipError_t e_ = (e); if (e_ != hipSuccess) return e_; } while (0)
+    SP_TRY(hx::launch_iota(s, pa, (uint32_t)N));
+    SP_TRY(hx::launch_gather_u64(s, (const unsigned long long*)d_ts, pa,
+                                 (unsigned long long*)d_ka, (uint32_t)N));
+    SP_TRY(hx::launch_xor_sign(s, (unsigned long long*)d_ka, (uint32_t)N));
+    SP_TRY(hx::sort_pairs_u64(s, d_ka, d_kb, pa, pb, N, d_temp, temp_cap));
+    SP_TRY(hx::launch_gather_u64(s, (const unsigned long long*)d_series, pb,
+                                 (unsigned long long*)d_ka, (uint32_t)N));
+    SP_TRY(hx::sort_pairs_u64(s, d_ka, d_kb, pb, pc, N, d_temp, temp_cap));
+#undef SP_TRY
+    return hipSuccess;
+}
+
 // GPU ingest sort (stable by (series, ts); equal PKs keep input order):
 // two stable LSD radix passes over a u32 permutation — ts (sign-biased),
 // then series — then a device gather and one D2H. Returns false on any HIP
@@ -2725,14 +2751,8 @@ static bool gpu_sort_batch(const uint64_t* series, const int64_t* ts,
     GS_TRY(hipMemcpyAsync(d_series, series, N * 8, hipMemcpyHostToDevice, s));
     GS_TRY(hipMemcpyAsync(d_ts, ts, N * 8, hipMemcpyHostToDevice, s));
     GS_TRY(hipMemcpyAsync(d_val, value, N * 8, hipMemcpyHostToDevice, s));
-    GS_TRY(hx::launch_iota(s, pa, (uint32_t)N));
-    GS_TRY(hx::launch_gather_u64(s, (const unsigned long long*)d_ts, pa,
-                                 (unsigned long long*)d_ka, (uint32_t)N));
-    GS_TRY(hx::launch_xor_sign(s, (unsigned long long*)d_ka, (uint32_t)N));
-    GS_TRY(hx::sort_pairs_u64(s, d_ka, d_kb, pa, pb, N, &d_temp, &temp_cap));
-    GS_TRY(hx::launch_gather_u64(s, (const unsigned long long*)d_series, pb,
-                                 (unsigned long long*)d_ka, (uint32_t)N));
-    GS_TRY(hx::sort_pairs_u64(s, d_ka, d_kb, pb, pc, N, &d_temp, &temp_cap));
+    GS_TRY(ingest_sort_perm(s, d_series, d_ts, d_ka, d_kb, pa, pb, pc, N,
+                            &d_temp, &temp_cap));
     const unsigned long long* srcs[3] = {
         (const unsigned long long*)d_series, (const unsigned long long*)d_ts,
         (const unsigned long long*)d_val};
@@ -2807,6 +2827,11 @@ static hx_status write_batch(hx_handle* h, const uint64_t* series,
     if (!h || !series || !ts || !value || n <= 0 || !out_seq)
         return fail(HX_ERR_INVALID, "bad argument");
     *out_seq = 0;
+    // an f64 SST in a Binary store would make the next hx_open refuse it
+    if (h->bytes_value)
+        return fail(HX_ERR_UNSUPPORTED,
+                    "the store's value column is Binary: write it with "
+                    "hx_write_bytes");
     if (enable_check) {
         // segment-crossing check (storage.rs:309-316). The reference uses
         // Rust truncating division on start/seg vs (end-1)/seg, where end
@@ -2907,7 +2932,8 @@ extern "C" hx_status hx_write_nullable(hx_handle* h, const uint64_t* series,
                                        const uint8_t* validity, int64_t n,
                                        int32_t enable_check,
                                        uint64_t* out_seq) {
-    if (h && out_seq && n > 0 && validity && !h->nullable_values) {
+    if (h && out_seq && n > 0 && validity && !h->nullable_values &&
+        !h->bytes_value) {   // a Binary store is refused by write_batch
         if (count_nulls(validity, n) > 0) {
             *out_seq = 0;
             return fail(HX_ERR_UNSUPPORTED,
@@ -2930,10 +2956,23 @@ extern "C" hx_status hx_write_nullable(hx_handle* h, const uint64_t* series,
 // (and seq) are gathered as before and kernel 1d packs the values per output
 // row group by the same permutation, so the host receives packed values,
 // bitmaps and counts, never the 8-byte validity words.
+static hx_status finish_compaction(hx_handle* h, const std::string& out_path,
+                                   uint64_t new_seq,
+                                   const std::vector<char>& in_set,
+                                   uint64_t* out_new_seq);
+static hx_status compact_rows_bytes(hx_handle* h, hx_prepared* P,
+                                    const std::vector<char>& in_set,
+                                    uint64_t max_seq, bool keep_seq,
+                                    uint64_t* out_new_seq);
+
 static hx_status compact_rows(hx_handle* h, hx_prepared* P,
                               const std::vector<char>& in_set,
                               uint64_t max_seq, bool keep_seq,
                               uint64_t* out_new_seq) {
+    // Binary value column: the value words are handles, not values
+    if (h->bytes_value)
+        return compact_rows_bytes(h, P, in_set, max_seq, keep_seq,
+                                  out_new_seq);
     DevPlan& plan = P->plans[0];
     const bool nullable = h->nullable_values != 0;
     const int32_t codec = h->write_codec;
@@ -3140,11 +3179,17 @@ static hx_status compact_rows(hx_handle* h, hx_prepared* P,
                                     kRowGroup, codec, ready);
     }
     if (!werr.empty()) return fail(HX_ERR_IO, werr);
+    return finish_compaction(h, out_path, new_seq, in_set, out_new_seq);
+}
 
-    // catalog update: add new file, drop + unlink inputs (add-before-delete,
-    // executor.rs:206-220)
+// catalog update: add new file, drop + unlink inputs (add-before-delete,
+// executor.rs:206-220)
+static hx_status finish_compaction(hx_handle* h, const std::string& out_path,
+                                   uint64_t new_seq,
+                                   const std::vector<char>& in_set,
+                                   uint64_t* out_new_seq) {
     CatSst fresh;
-    st = read_file_meta(out_path, new_seq, fresh);
+    hx_status st = read_file_meta(out_path, new_seq, fresh);
     if (st != HX_OK) return st;
     std::vector<CatSst> kept;
     for (size_t i = 0; i < h->ssts.size(); i++) {
@@ -3160,6 +3205,586 @@ static hx_status compact_rows(hx_handle* h, hx_prepared* P,
     h->ssts = std::move(kept);
     *out_new_seq = new_seq;
     return HX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Binary value stores (BytesMergeOperator / UpdateMode::Append schema): the
+// write side. Values travel as handles (off << 20 | len, k_ba_offsets'
+// format) and kernel 1f (or its host twin, ba_pages.h) turns them into the
+// PLAIN BYTE_ARRAY page images write_metric_sst_bytes takes ready-made.
+// ---------------------------------------------------------------------------
+namespace {
+
+const char kBaLimit[] =
+    "2^20 - 1 bytes (a value handle has 20 length bits)";
+
+// The one refusal of a value page above Parquet's i32 page sizes (and
+// BaPageDesc::src_len): page_off has n_pages + 1 entries.
+hx_status check_page_sizes(const uint64_t* page_off, uint64_t n_pages) {
+    for (uint64_t g = 0; g < n_pages; g++)
+        if (page_off[g + 1] - page_off[g] > hx::BA_MAX_PAGE_BYTES)
+            return fail(HX_ERR_UNSUPPORTED,
+                        "row group " + std::to_string(g) + ": the value "
+                        "page would exceed INT32_MAX bytes (multi-page "
+                        "chunks are not written)");
+    return HX_OK;
+}
+
+// argument check shared by hx_debug_ba_pages and hx_debug_ba_pages_host
+bool ba_debug_args_ok(const uint8_t* src, uint64_t src_size,
+                      const uint64_t* handles, uint32_t n_src,
+                      uint32_t row_group, const uint64_t* page_off,
+                      const uint64_t* n_errors, const uint64_t* n_over_cap) {
+    return page_off && n_errors && n_over_cap && row_group != 0 &&
+           row_group <= hx::BA_MAX_ROW_GROUP && (!n_src || handles) &&
+           (!src_size || src);
+}
+
+struct DevBufs {
+    std::vector<void*> p;
+    ~DevBufs() {
+        for (void* q : p)
+            if (q) (void)hipFree(q);
+    }
+    hipError_t alloc(void** out, size_t bytes) {
+        hipError_t e = hipMalloc(out, bytes ? bytes : 1);
+        if (e == hipSuccess) p.push_back(*out);
+        return e;
+    }
+};
+
+// The size pass of kernel 1f with its device buffers, and what the caller
+// must refuse before anything is written: rows the kernel refused, Append
+// groups above the value limit, page images above Parquet's i32 sizes.
+struct BaPageBuilder {
+    DevBufs dev;
+    uint32_t* d_row_len = nullptr;
+    unsigned long long* d_words = nullptr;   // page_off[n_pages + 1],
+                                             // counts[2], page_size[n_pages]
+    uint32_t n_pages = 0;
+    std::vector<uint64_t> page_off;          // n_pages + 1, counts behind
+    uint64_t n_errors = 0, n_over_cap = 0;
+
+    uint64_t total() const { return page_off[n_pages]; }
+
+    // launches, one small D2H, no verdict yet
+    hx_status run(hipStream_t s, uint64_t src_size, const uint64_t* d_handles,
+                  const uint32_t* d_group_start, uint32_t n_src,
+                  uint32_t n_out, uint32_t row_group) {
+        n_pages = (uint32_t)hx::ba_n_pages(n_out, row_group);
+        HIP_TRY(dev.alloc((void**)&d_row_len, size_t(n_out) * 4));
+        HIP_TRY(dev.alloc((void**)&d_words, (2 * size_t(n_pages) + 3) * 8));
+        unsigned long long* d_counts = d_words + n_pages + 1;
+        HIP_TRY(hipMemsetAsync(d_counts, 0, 16, s));
+        HIP_TRY(hx::launch_ba_page_sizes(s, src_size, d_handles,
+                                         d_group_start, n_src, n_out,
+                                         row_group, d_row_len, d_counts + 2,
+                                         d_words, d_counts));
+        page_off.resize(size_t(n_pages) + 3);
+        HIP_TRY(hipMemcpyAsync(page_off.data(), d_words,
+                               (size_t(n_pages) + 3) * 8,
+                               hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        n_errors = page_off[n_pages + 1];
+        n_over_cap = page_off[n_pages + 2];
+        return HX_OK;
+    }
+
+    hx_status verdict() const {
+        if (n_errors)
+            return fail(HX_ERR_FORMAT,
+                        "byte pages: a value handle does not fit its source "
+                        "or the group bounds are out of order");
+        if (n_over_cap)
+            return fail(HX_ERR_UNSUPPORTED,
+                        std::string("an Append group's concatenated value "
+                                    "exceeds ") + kBaLimit);
+        return check_page_sizes(page_off.data(), n_pages);
+    }
+};
+
+// ready table of the 5-column metric layout: the value column's page images
+std::vector<hx::PagePayload> ba_ready(const uint64_t* page_off,
+                                      uint32_t n_pages,
+                                      const uint8_t* image) {
+    std::vector<hx::PagePayload> r(size_t(n_pages) * 5, hx::PagePayload{});
+    for (uint32_t g = 0; g < n_pages; g++) {
+        r[size_t(g) * 5 + 2].ptr = image + page_off[g];
+        r[size_t(g) * 5 + 2].len = uint32_t(page_off[g + 1] - page_off[g]);
+    }
+    return r;
+}
+
+// (bytes, offsets) batches of hx_write_bytes / hx_write_sst_bytes
+hx_status check_value_offsets(const int64_t* offsets, int64_t n) {
+    if (offsets[0] < 0) return fail(HX_ERR_INVALID, "negative offset");
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t l = offsets[i + 1] - offsets[i];
+        if (l < 0) return fail(HX_ERR_INVALID, "offsets decrease");
+        if (l > (int64_t)hx::BA_MAX_VALUE_LEN)
+            return fail(HX_ERR_INVALID,
+                        "row " + std::to_string(i) + ": value of " +
+                            std::to_string(l) + " bytes; the limit is " +
+                            kBaLimit);
+        if (uint64_t(offsets[i]) >= (1ull << 44))
+            return fail(HX_ERR_INVALID, "batch above 2^44 value bytes");
+    }
+    return HX_OK;
+}
+
+}  // namespace
+
+extern "C" hx_status hx_write_sst_bytes(const char* path,
+                                        const uint64_t* series,
+                                        const int64_t* ts,
+                                        const uint8_t* bytes,
+                                        const int64_t* offsets,
+                                        const uint64_t* seqs, uint64_t seq,
+                                        int64_t n_rows, int64_t row_group) {
+    if (!path || !series || !ts || !offsets || n_rows <= 0 || row_group <= 0)
+        return fail(HX_ERR_INVALID, "bad argument");
+    hx_status st = check_value_offsets(offsets, n_rows);
+    if (st != HX_OK) return st;
+    if (!bytes && offsets[n_rows] != offsets[0])
+        return fail(HX_ERR_INVALID, "bad argument");
+    // from the offsets alone, before a value byte is read
+    std::vector<uint64_t> page_off(1, 0);
+    for (int64_t base = 0; base < n_rows; base += row_group) {
+        const int64_t rows = std::min<int64_t>(row_group, n_rows - base);
+        page_off.push_back(page_off.back() + 4ull * rows +
+                           uint64_t(offsets[base + rows] - offsets[base]));
+    }
+    st = check_page_sizes(page_off.data(), page_off.size() - 1);
+    if (st != HX_OK) return st;
+    std::string err = hx::write_metric_sst_bytes(path, series, ts, bytes,
+                                                 offsets, seqs, seq, n_rows,
+                                                 row_group);
+    if (!err.empty()) return fail(HX_ERR_IO, err);
+    return HX_OK;
+}
+
+extern "C" hx_status hx_debug_ba_pages_host(
+    const uint8_t* src, uint64_t src_size, const uint64_t* handles,
+    uint32_t n_src, const uint32_t* group_start, uint32_t n_out,
+    uint32_t row_group, uint64_t* page_off, uint8_t* out, uint64_t out_cap,
+    uint64_t* n_errors, uint64_t* n_over_cap) {
+    if (!ba_debug_args_ok(src, src_size, handles, n_src, row_group, page_off,
+                          n_errors, n_over_cap))
+        return fail(HX_ERR_INVALID, "bad argument");
+    std::vector<uint32_t> row_len(n_out);
+    hx::BaPagesCounts c = hx::ba_page_sizes_host(
+        src_size, handles, n_src, group_start, n_out, row_group,
+        row_len.data(), page_off);
+    *n_errors = c.n_errors;
+    *n_over_cap = c.n_over_cap;
+    const uint64_t total = page_off[hx::ba_n_pages(n_out, row_group)];
+    if (!out) return HX_OK;
+    if (out_cap != total)
+        return fail(HX_ERR_INVALID, "out_cap is not the image size");
+    hx::ba_build_pages_host(src, src_size, handles, n_src, group_start, n_out,
+                            row_group, row_len.data(), page_off, out);
+    return HX_OK;
+}
+
+extern "C" hx_status hx_debug_ba_pages(
+    const uint8_t* src, uint64_t src_size, const uint64_t* handles,
+    uint32_t n_src, const uint32_t* group_start, uint32_t n_out,
+    uint32_t row_group, uint64_t* page_off, uint8_t* out, uint64_t out_cap,
+    uint64_t* n_errors, uint64_t* n_over_cap) {
+    if (!ba_debug_args_ok(src, src_size, handles, n_src, row_group, page_off,
+                          n_errors, n_over_cap))
+        return fail(HX_ERR_INVALID, "bad argument");
+    // every buffer exactly as large as the contract says it is
+    DevBufs dev;
+    uint8_t* d_src = nullptr;
+    uint64_t* d_handles = nullptr;
+    uint32_t* d_gs = nullptr;
+    uint8_t* d_out = nullptr;
+    HIP_TRY(dev.alloc((void**)&d_src, src_size));
+    HIP_TRY(dev.alloc((void**)&d_handles, size_t(n_src) * 8));
+    if (src_size)
+        HIP_TRY(hipMemcpy(d_src, src, src_size, hipMemcpyHostToDevice));
+    if (n_src)
+        HIP_TRY(hipMemcpy(d_handles, handles, size_t(n_src) * 8,
+                          hipMemcpyHostToDevice));
+    if (group_start) {
+        HIP_TRY(dev.alloc((void**)&d_gs, (size_t(n_out) + 1) * 4));
+        HIP_TRY(hipMemcpy(d_gs, group_start, (size_t(n_out) + 1) * 4,
+                          hipMemcpyHostToDevice));
+    }
+    BaPageBuilder b;
+    hx_status st = b.run(nullptr, src_size, d_handles, d_gs, n_src, n_out,
+                         row_group);
+    if (st != HX_OK) return st;
+    std::memcpy(page_off, b.page_off.data(), (size_t(b.n_pages) + 1) * 8);
+    *n_errors = b.n_errors;
+    *n_over_cap = b.n_over_cap;
+    if (!out) return HX_OK;
+    if (out_cap != b.total())
+        return fail(HX_ERR_INVALID, "out_cap is not the image size");
+    HIP_TRY(dev.alloc((void**)&d_out, b.total()));
+    if (b.total()) HIP_TRY(hipMemset(d_out, 0xEE, b.total()));
+    HIP_TRY(hx::launch_ba_build_pages(nullptr, d_src, src_size, d_handles,
+                                      d_gs, n_src, n_out, row_group,
+                                      b.d_row_len, b.d_words, d_out));
+    HIP_TRY(hipDeviceSynchronize());
+    if (b.total())
+        HIP_TRY(hipMemcpy(out, d_out, b.total(), hipMemcpyDeviceToHost));
+    return HX_OK;
+}
+
+// The device route of hx_write_bytes: the ingest sort's permutation (two
+// stable LSD passes, ts then series), the handles gathered by it, kernel 1f
+// over the uploaded value bytes, and ONE copy back: sorted series, sorted ts
+// and the page images, in that order in `host`.
+static hx_status gpu_write_bytes(const uint64_t* series, const int64_t* ts,
+                                 const uint8_t* bytes, uint64_t n_bytes,
+                                 const std::vector<uint64_t>& handles,
+                                 int64_t n, std::vector<uint8_t>& host,
+                                 std::vector<uint64_t>& page_off) {
+    hipStream_t s = nullptr;
+    const size_t N = (size_t)n;
+    DevBufs dev;
+    void* d_temp = nullptr;
+    size_t temp_cap = 0;
+    struct TempGuard {
+        void** t;
+        ~TempGuard() { if (*t) (void)hipFree(*t); }
+    } temp_guard{&d_temp};
+    uint64_t *d_series, *d_ts, *d_h, *d_ka, *d_kb, *d_hs;
+    uint32_t *pa, *pb, *pc;
+    uint8_t *d_bytes, *d_final;
+    HIP_TRY(dev.alloc((void**)&d_series, N * 8));
+    HIP_TRY(dev.alloc((void**)&d_ts, N * 8));
+    HIP_TRY(dev.alloc((void**)&d_h, N * 8));
+    HIP_TRY(dev.alloc((void**)&d_ka, N * 8));
+    HIP_TRY(dev.alloc((void**)&d_kb, N * 8));
+    HIP_TRY(dev.alloc((void**)&d_hs, N * 8));
+    HIP_TRY(dev.alloc((void**)&pa, N * 4));
+    HIP_TRY(dev.alloc((void**)&pb, N * 4));
+    HIP_TRY(dev.alloc((void**)&pc, N * 4));
+    HIP_TRY(dev.alloc((void**)&d_bytes, n_bytes));
+    HIP_TRY(hipMemcpyAsync(d_series, series, N * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_ts, ts, N * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_h, handles.data(), N * 8, hipMemcpyHostToDevice,
+                           s));
+    if (n_bytes)
+        HIP_TRY(hipMemcpyAsync(d_bytes, bytes, n_bytes, hipMemcpyHostToDevice,
+                               s));
+    HIP_TRY(ingest_sort_perm(s, d_series, (const int64_t*)d_ts, d_ka, d_kb,
+                             pa, pb, pc, N, &d_temp, &temp_cap));
+    HIP_TRY(hx::launch_gather_u64(s, (const unsigned long long*)d_h, pc,
+                                  (unsigned long long*)d_hs, (uint32_t)N));
+    BaPageBuilder b;
+    hx_status st = b.run(s, n_bytes, d_hs, nullptr, (uint32_t)N, (uint32_t)N,
+                         (uint32_t)kRowGroup);
+    if (st == HX_OK) st = b.verdict();
+    if (st != HX_OK) return st;
+    const size_t key_bytes = 2 * N * 8;
+    HIP_TRY(dev.alloc((void**)&d_final, key_bytes + b.total()));
+    const unsigned long long* srcs[2] = {
+        (const unsigned long long*)d_series, (const unsigned long long*)d_ts};
+    HIP_TRY(hx::launch_gather_multi(s, srcs, 2, pc,
+                                    (unsigned long long*)d_final,
+                                    (uint32_t)N));
+    HIP_TRY(hx::launch_ba_build_pages(s, d_bytes, n_bytes, d_hs, nullptr,
+                                      (uint32_t)N, (uint32_t)N,
+                                      (uint32_t)kRowGroup, b.d_row_len,
+                                      b.d_words, d_final + key_bytes));
+    host.resize(key_bytes + b.total());
+    HIP_TRY(hipMemcpyAsync(host.data(), d_final, host.size(),
+                           hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    page_off.assign(b.page_off.begin(), b.page_off.begin() + b.n_pages + 1);
+    return HX_OK;
+}
+
+extern "C" hx_status hx_write_bytes(hx_handle* h, const uint64_t* series,
+                                    const int64_t* ts, const uint8_t* bytes,
+                                    const int64_t* offsets, int64_t n,
+                                    int32_t enable_check, uint64_t* out_seq) {
+    // ColumnarStorage::write (storage.rs:76-89, :307-333) for the Binary
+    // schema: segment check, stable PK sort (equal PKs keep batch order — the
+    // scan's Append key (seq << 32 | file row) depends on it), file id =
+    // sequence, catalog add.
+    if (!h || !series || !ts || !offsets || n <= 0 || !out_seq)
+        return fail(HX_ERR_INVALID, "bad argument");
+    *out_seq = 0;
+    if (n > 0xFFFFFFFFll)
+        return fail(HX_ERR_UNSUPPORTED, "batches above 2^32 rows");
+    if (!h->bytes_value && !h->ssts.empty())
+        return fail(HX_ERR_SCHEMA,
+                    "hx_write_bytes: the store's value column is f64");
+    if (h->nullable_values || h->write_codec)
+        return fail(HX_ERR_UNSUPPORTED,
+                    "hx_write_bytes: nullable values and write codecs need "
+                    "an f64 value column");
+    hx_status st = check_value_offsets(offsets, n);
+    if (st != HX_OK) return st;
+    if (!bytes && offsets[n] != offsets[0])
+        return fail(HX_ERR_INVALID, "bad argument");
+    if (enable_check) {
+        int64_t mn = ts[0], mx = ts[0];
+        for (int64_t i = 1; i < n; i++) {
+            mn = std::min(mn, ts[i]);
+            mx = std::max(mx, ts[i]);
+        }
+        if (mn / h->segment_ms != mx / h->segment_ms)
+            return fail(HX_ERR_INVALID,
+                        "write crosses a segment boundary (storage.rs:309-316)");
+    }
+    // handles relative to bytes + offsets[0]
+    const uint8_t* src = bytes ? bytes + offsets[0] : nullptr;
+    const uint64_t n_bytes = uint64_t(offsets[n] - offsets[0]);
+    std::vector<uint64_t> handles(n);
+    for (int64_t i = 0; i < n; i++)
+        handles[i] = (uint64_t(offsets[i] - offsets[0]) << hx::BA_LEN_BITS) |
+                     uint64_t(offsets[i + 1] - offsets[i]);
+    std::vector<uint8_t> host;        // sorted series, sorted ts, page images
+    std::vector<uint64_t> page_off;
+    const size_t N = (size_t)n;
+    if (n >= (1 << 16) && hip_device_count() > 0) {
+        st = gpu_write_bytes(series, ts, src, n_bytes, handles, n, host,
+                             page_off);
+        if (st != HX_OK) return st;
+    } else {
+        std::vector<uint32_t> order(n);
+        for (int64_t i = 0; i < n; i++) order[i] = (uint32_t)i;
+        std::stable_sort(order.begin(), order.end(),
+                         [&](uint32_t a2, uint32_t b2) {
+                             if (series[a2] != series[b2])
+                                 return series[a2] < series[b2];
+                             return ts[a2] < ts[b2];
+                         });
+        std::vector<uint64_t> hs(n);
+        for (int64_t i = 0; i < n; i++) hs[i] = handles[order[i]];
+        const uint64_t n_pages = hx::ba_n_pages(N, kRowGroup);
+        std::vector<uint32_t> row_len(n);
+        page_off.resize(n_pages + 1);
+        hx::ba_page_sizes_host(n_bytes, hs.data(), N, nullptr, N, kRowGroup,
+                               row_len.data(), page_off.data());
+        st = check_page_sizes(page_off.data(), n_pages);
+        if (st != HX_OK) return st;
+        host.resize(2 * N * 8 + page_off[n_pages]);
+        uint64_t* s2 = (uint64_t*)host.data();
+        int64_t* t2 = (int64_t*)(host.data() + N * 8);
+        for (int64_t i = 0; i < n; i++) {
+            s2[i] = series[order[i]];
+            t2[i] = ts[order[i]];
+        }
+        hx::ba_build_pages_host(src, n_bytes, hs.data(), N, nullptr, N,
+                                kRowGroup, row_len.data(), page_off.data(),
+                                host.data() + 2 * N * 8);
+    }
+    uint64_t max_seq = 0;
+    for (const auto& s : h->ssts) max_seq = std::max(max_seq, s.seq);
+    const uint64_t new_seq = max_seq + 1;
+    std::string out_path = h->store + "/data/" + std::to_string(new_seq) +
+                           ".sst";
+    std::vector<hx::PagePayload> ready =
+        ba_ready(page_off.data(), (uint32_t)(page_off.size() - 1),
+                 host.data() + 2 * N * 8);
+    std::string werr = hx::write_metric_sst_bytes(
+        out_path, (const uint64_t*)host.data(),
+        (const int64_t*)(host.data() + N * 8), nullptr, nullptr, nullptr,
+        new_seq, n, kRowGroup, ready.data());
+    if (!werr.empty()) return fail(HX_ERR_IO, werr);
+    CatSst fresh;
+    st = read_file_meta(out_path, new_seq, fresh);
+    if (st != HX_OK) return st;
+    h->bytes_value = true;
+    h->ssts.push_back(std::move(fresh));
+    *out_seq = new_seq;
+    return HX_OK;
+}
+
+// compact_rows for a Binary value column. The row stream's value words are
+// handles into the staged blob. Overwrite: survivors as the f64 path (last
+// wins), the winner's handle. Append: every row is kept, a leading stable
+// pass on the packed (seq << 32 | file row) key exactly as hx_scan runs it,
+// then ts, then series; equal-PK runs become ONE output row whose value is
+// the concatenation in that order and whose sequence (keep_seq) is that of
+// the run's FIRST row (BytesMergeOperator takes element 0 of every non-value
+// column, operator.rs:99-102, and under keep_builtin __seq__ is one). Kernel
+// 1f builds the page images from the blob; value bytes never cross PCIe as
+// rows: one D2H of the output rows' key columns and the page images.
+static hx_status compact_rows_bytes(hx_handle* h, hx_prepared* P,
+                                    const std::vector<char>& in_set,
+                                    uint64_t max_seq, bool keep_seq,
+                                    uint64_t* out_new_seq) {
+    DevPlan& plan = P->plans[0];
+    const bool append = h->update_mode == 1;
+    if (append)
+        for (const auto& c : h->ssts)
+            if (c.seq >= (1ull << 32))
+                return fail(HX_ERR_UNSUPPORTED,
+                            "append stores need file sequences < 2^32");
+    HIP_TRY(hipSetDevice(plan.device));
+    hipStream_t s = plan.stream;
+    hx_status st = ensure_decoded(plan, s);
+    if (st != HX_OK) return st;
+    const uint64_t cap = (uint64_t)plan.rows_scanned;
+    if (cap == 0) return HX_OK;
+    if (cap > 0xFFFFFFFFull)
+        return fail(HX_ERR_UNSUPPORTED,
+                    "row streams above 2^32 rows per call: split the range");
+    const bool want_seq = keep_seq || append;
+    size_t need = cap * 8 * (5 + (want_seq ? 1 : 0)) + cap * 4 * 3 + 64;
+    st = ensure_dev(&plan.d_scratch, &plan.scratch_cap, need);
+    if (st != HX_OK) return st;
+    uint8_t* base = (uint8_t*)plan.d_scratch;
+    auto carve8 = [&](size_t count) {
+        uint8_t* p = base;
+        base += (count * 8 + 7) & ~size_t(7);
+        return p;
+    };
+    uint64_t* d_series = (uint64_t*)carve8(cap);
+    long long* d_ts = (long long*)carve8(cap);
+    double* d_val = (double*)carve8(cap);
+    uint64_t* d_seq = want_seq ? (uint64_t*)carve8(cap) : nullptr;
+    uint64_t* d_keys = (uint64_t*)carve8(cap);
+    uint64_t* d_keys_out = (uint64_t*)carve8(cap);
+    unsigned long long* d_cursor = (unsigned long long*)carve8(1);
+    uint32_t* perm_a = (uint32_t*)base; base += cap * 4;
+    uint32_t* perm_b = (uint32_t*)base; base += cap * 4;
+    uint32_t* perm_c = (uint32_t*)base; base += cap * 4;
+
+    HIP_TRY(hipMemsetAsync(d_cursor, 0, 8, s));
+    hx::AggParams A = base_params(P, plan);
+    A.keep_dups = append ? 1 : 0;
+    HIP_TRY(hx::launch_scan_rows(s, A, 0, A.n_rgs, d_series, d_ts, d_val,
+                                 d_cursor, cap, d_seq, append ? 1 : 0,
+                                 nullptr));
+    unsigned long long n64 = 0;
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpy(&n64, d_cursor, 8, hipMemcpyDeviceToHost));
+    if (n64 > cap) return fail(HX_ERR_HIP, "compact row buffer overflow");
+    const uint32_t n = (uint32_t)n64;
+    if (n == 0) return HX_OK;
+
+    HIP_TRY(hx::launch_iota(s, perm_a, n));
+    if (append) {
+        HIP_TRY(hx::launch_gather_u64(s, (const unsigned long long*)d_seq,
+                                      perm_a, (unsigned long long*)d_keys,
+                                      n));
+        HIP_TRY(hx::sort_pairs_u64(s, d_keys, d_keys_out, perm_a, perm_b, n,
+                                   &plan.d_sort_temp, &plan.sort_temp_cap));
+        std::swap(perm_a, perm_b);
+    }
+    HIP_TRY(hx::launch_gather_u64(s, (const unsigned long long*)d_ts, perm_a,
+                                  (unsigned long long*)d_keys, n));
+    HIP_TRY(hx::launch_xor_sign(s, (unsigned long long*)d_keys, n));
+    HIP_TRY(hx::sort_pairs_u64(s, d_keys, d_keys_out, perm_a, perm_b, n,
+                               &plan.d_sort_temp, &plan.sort_temp_cap));
+    HIP_TRY(hx::launch_gather_u64(s, (const unsigned long long*)d_series,
+                                  perm_b, (unsigned long long*)d_keys, n));
+    HIP_TRY(hx::sort_pairs_u64(s, d_keys, d_keys_out, perm_b, perm_c, n,
+                               &plan.d_sort_temp, &plan.sort_temp_cap));
+    const uint32_t* perm = perm_c;
+
+    // sorted rows: series, ts, handle [, seq (Overwrite)]
+    DevBufs dev;
+    const uint32_t n_sorted = (keep_seq && !append) ? 4 : 3;
+    unsigned long long* d_sorted = nullptr;
+    HIP_TRY(dev.alloc((void**)&d_sorted, size_t(n_sorted) * n * 8));
+    const unsigned long long* srcs[4] = {
+        (const unsigned long long*)d_series, (const unsigned long long*)d_ts,
+        (const unsigned long long*)d_val, (const unsigned long long*)d_seq};
+    HIP_TRY(hx::launch_gather_multi(s, srcs, n_sorted, perm, d_sorted, n));
+    const uint64_t* d_handles = (const uint64_t*)(d_sorted + 2 * size_t(n));
+
+    // output rows' key columns on the device, and the group bounds
+    const unsigned long long* k_series = d_sorted;
+    const unsigned long long* k_ts = d_sorted + n;
+    const unsigned long long* k_seq = keep_seq ? d_sorted + 3 * size_t(n)
+                                               : nullptr;
+    uint32_t* d_gs = nullptr;
+    uint32_t n_out = n;
+    if (append) {
+        uint32_t *d_flag, *d_rank;
+        unsigned long long *d_heads, *d_nout;
+        HIP_TRY(dev.alloc((void**)&d_flag, size_t(n) * 4));
+        HIP_TRY(dev.alloc((void**)&d_rank, size_t(n) * 4));
+        HIP_TRY(dev.alloc((void**)&d_gs, (size_t(n) + 1) * 4));
+        HIP_TRY(dev.alloc((void**)&d_heads, 3 * size_t(n) * 8));
+        HIP_TRY(dev.alloc((void**)&d_nout, 8));
+        HIP_TRY(hx::launch_group_heads(
+            s, d_sorted, d_sorted + n,
+            keep_seq ? (const unsigned long long*)d_seq : nullptr, perm, n,
+            d_flag, d_rank, d_gs, d_heads, d_heads + n,
+            d_heads + 2 * size_t(n), d_nout, &plan.d_sort_temp,
+            &plan.sort_temp_cap));
+        unsigned long long no = 0;
+        HIP_TRY(hipMemcpyAsync(&no, d_nout, 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (no == 0 || no > n)
+            return fail(HX_ERR_HIP, "compact: group count out of range");
+        n_out = (uint32_t)no;
+        k_series = d_heads;
+        k_ts = d_heads + n;
+        k_seq = keep_seq ? d_heads + 2 * size_t(n) : nullptr;
+    }
+
+    // HX_DEBUG: one event pair around the page-build launches
+    const bool timed = getenv("HX_DEBUG") != nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    struct EvGuard {
+        hipEvent_t* e;
+        ~EvGuard() {
+            for (int i = 0; i < 2; i++)
+                if (e[i]) (void)hipEventDestroy(e[i]);
+        }
+    } ev_guard{ev};
+    if (timed) {
+        for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
+        HIP_TRY(hipEventRecord(ev[0], s));
+    }
+    BaPageBuilder b;
+    st = b.run(s, plan.blob_bytes, d_handles, d_gs, n, n_out,
+               (uint32_t)kRowGroup);
+    if (st == HX_OK) st = b.verdict();
+    if (st != HX_OK) return st;   // nothing written, nothing unlinked
+    const size_t n_keys = keep_seq ? 3 : 2;
+    const size_t key_bytes = n_keys * size_t(n_out) * 8;
+    uint8_t* d_final = nullptr;
+    HIP_TRY(dev.alloc((void**)&d_final, key_bytes + b.total()));
+    HIP_TRY(hx::launch_ba_build_pages(s, plan.d_blob, plan.blob_bytes,
+                                      d_handles, d_gs, n, n_out,
+                                      (uint32_t)kRowGroup, b.d_row_len,
+                                      b.d_words, d_final + key_bytes));
+    if (timed) HIP_TRY(hipEventRecord(ev[1], s));
+    const unsigned long long* keys[3] = {k_series, k_ts, k_seq};
+    for (size_t k = 0; k < n_keys; k++)
+        HIP_TRY(hipMemcpyAsync(d_final + k * size_t(n_out) * 8, keys[k],
+                               size_t(n_out) * 8, hipMemcpyDeviceToDevice,
+                               s));
+    std::vector<uint8_t> host(key_bytes + b.total());
+    HIP_TRY(hipMemcpyAsync(host.data(), d_final, host.size(),
+                           hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (timed) {
+        float pages_ms = 0;
+        HIP_TRY(hipEventElapsedTime(&pages_ms, ev[0], ev[1]));
+        fprintf(stderr,
+                "[hx] compact_bytes rows=%u out_rows=%u append=%d "
+                "keep_seq=%d pages=%u pages_ms=%.4f d2h_bytes=%zu\n",
+                n, n_out, int(append), int(keep_seq), b.n_pages, pages_ms,
+                host.size() + (size_t(b.n_pages) + 3) * 8 +
+                    (append ? 8 : 0) + 8);
+    }
+
+    const uint64_t new_seq = max_seq + 1;
+    std::string out_path = h->store + "/data/" + std::to_string(new_seq) +
+                           ".sst";
+    std::vector<hx::PagePayload> ready =
+        ba_ready(b.page_off.data(), b.n_pages, host.data() + key_bytes);
+    const uint64_t* hk = (const uint64_t*)host.data();
+    std::string werr = hx::write_metric_sst_bytes(
+        out_path, hk, (const int64_t*)(hk + n_out), nullptr, nullptr,
+        keep_seq ? hk + 2 * size_t(n_out) : nullptr, new_seq, n_out,
+        kRowGroup, ready.data());
+    if (!werr.empty()) return fail(HX_ERR_IO, werr);
+    return finish_compaction(h, out_path, new_seq, in_set, out_new_seq);
 }
 
 extern "C" hx_status hx_compact(hx_handle* h, hx_time_range range,

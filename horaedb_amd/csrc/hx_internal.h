@@ -65,6 +65,30 @@ extern "C" uint64_t hx_debug_snappy_compress_host(const uint8_t* src,
                                                   uint64_t cap);
 
 // Test hook (exported, not part of the public C-ABI): run the production
+// launches of kernel 1f (hx::launch_ba_page_sizes, then
+// hx::launch_ba_build_pages; hx_kernels.h, contract in ba_pages.h) once over
+// caller-built arrays on the current device. src: src_size bytes; handles:
+// n_src words (off << 20 | len relative to src, in output order);
+// group_start: n_out + 1 entries or NULL; row_group <= 8192. page_off
+// receives ceil(n_out / row_group) + 1 entries, *n_errors the refused handles
+// and group_start pairs, *n_over_cap the rows above 2^20 - 1 bytes. With out
+// NULL only the size pass runs; otherwise out_cap must equal the last
+// page_off entry, the image is built in a device buffer of exactly that size
+// (pre-filled with 0xEE) and copied back whole, refused rows as empty values.
+// Every device buffer is exactly as large as stated here.
+// hx_debug_ba_pages_host is the same over the host twin, no GPU needed.
+extern "C" hx_status hx_debug_ba_pages(
+    const uint8_t* src, uint64_t src_size, const uint64_t* handles,
+    uint32_t n_src, const uint32_t* group_start, uint32_t n_out,
+    uint32_t row_group, uint64_t* page_off, uint8_t* out, uint64_t out_cap,
+    uint64_t* n_errors, uint64_t* n_over_cap);
+extern "C" hx_status hx_debug_ba_pages_host(
+    const uint8_t* src, uint64_t src_size, const uint64_t* handles,
+    uint32_t n_src, const uint32_t* group_start, uint32_t n_out,
+    uint32_t row_group, uint64_t* page_off, uint8_t* out, uint64_t out_cap,
+    uint64_t* n_errors, uint64_t* n_over_cap);
+
+// Test hook (exported, not part of the public C-ABI): run the production
 // launch of kernel 1e (hx::launch_snappy_compress, hx_kernels.h) once over
 // n_pages caller-built pages on the current device. Page i is pages[offs[i],
 // offs[i] + lens[i]); it is uploaded at a 64-byte-aligned device address plus

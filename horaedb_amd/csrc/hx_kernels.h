@@ -139,6 +139,45 @@ hipError_t launch_tag_filter(hipStream_t s, const TagFilterParams& f);
 hipError_t launch_copy_bytes(hipStream_t s, const uint8_t* blob,
                              const uint64_t* handles, const int64_t* dst_off,
                              uint8_t* out, uint32_t n);
+// Kernel 1f (ba_pages.h states the contract and is its host twin): PLAIN
+// BYTE_ARRAY page images from per-row handles (off << 20 | len relative to
+// src, in output order), output row groups of row_group <= 8192 rows, else
+// hipErrorInvalidValue. group_start: n_out + 1 entries or null.
+// launch_ba_page_sizes writes row_len[n_out], page_size[n_pages] and the
+// exclusive scan page_off[n_pages + 1], and adds to counts[0] (bad handles
+// and group_start pairs) and counts[1] (rows above BA_MAX_VALUE_LEN).
+// launch_ba_build_pages then writes the image, page_off[n_pages] bytes.
+hipError_t launch_ba_page_sizes(hipStream_t s, uint64_t src_size,
+                                const uint64_t* handles,
+                                const uint32_t* group_start, uint32_t n_src,
+                                uint32_t n_out, uint32_t row_group,
+                                uint32_t* row_len,
+                                unsigned long long* page_size,
+                                unsigned long long* page_off,
+                                unsigned long long* counts);
+hipError_t launch_ba_build_pages(hipStream_t s, const uint8_t* src,
+                                 uint64_t src_size, const uint64_t* handles,
+                                 const uint32_t* group_start, uint32_t n_src,
+                                 uint32_t n_out, uint32_t row_group,
+                                 const uint32_t* row_len,
+                                 const unsigned long long* page_off,
+                                 uint8_t* out);
+// Equal-PK runs of n sorted rows (n > 0): flag and rank are n words of
+// scratch; group_start gets n_out + 1 entries (room for n + 1), the head
+// columns one entry per run, *n_out the run count. seq_key (may be null):
+// the UNSORTED rows' (seq << 32 | file row) keys, read through perm; a run's
+// head_seq is the sequence of its first row.
+hipError_t launch_group_heads(hipStream_t s, const unsigned long long* series,
+                              const unsigned long long* ts,
+                              const unsigned long long* seq_key,
+                              const uint32_t* perm, uint32_t n,
+                              uint32_t* flag, uint32_t* rank,
+                              uint32_t* group_start,
+                              unsigned long long* head_series,
+                              unsigned long long* head_ts,
+                              unsigned long long* head_seq,
+                              unsigned long long* n_out, void** d_temp,
+                              size_t* temp_bytes);
 hipError_t launch_tsid_intersect(hipStream_t s, const uint64_t* a,
                                  unsigned long long n_a, const uint64_t* b,
                                  unsigned long long n_b, uint64_t* out,

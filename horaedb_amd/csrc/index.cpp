@@ -90,6 +90,16 @@ extern "C" hx_status hx_index_write(hx_handle* h, const uint64_t* metric_id,
     if (!h || !tag_keys || !tag_values || !tsids || n <= 0 || !out_seq)
         return set_error(HX_ERR_INVALID, "hx_index_write: bad argument");
     *out_seq = 0;
+    // the query side reads keys and values through handles with 20 length
+    // bits (k_ba_offsets): a longer one would be a file it cannot read
+    for (int64_t i = 0; i < n; i++)
+        if (!tag_keys[i] || !tag_values[i] ||
+            strlen(tag_keys[i]) >= (size_t(1) << 20) ||
+            strlen(tag_values[i]) >= (size_t(1) << 20))
+            return set_error(HX_ERR_INVALID,
+                             "hx_index_write: a tag key or value is missing "
+                             "or reaches 2^20 bytes (the limit is 2^20 - 1, "
+                             "a value handle has 20 length bits)");
     // PK sort (tag_key, tag_value, tsid) — the RFC index table order
     std::vector<uint32_t> order(n);
     std::iota(order.begin(), order.end(), 0u);
@@ -356,7 +366,8 @@ extern "C" hx_status hx_index_query(hx_handle* h, const hx_tag_pred* preds,
     if (ba_err)
         return set_error(HX_ERR_FORMAT,
                          "index BYTE_ARRAY page walk failed (malformed "
-                         "length prefix)");
+                         "length prefix, or a value of 2^20 bytes or more: "
+                         "a value handle has 20 length bits)");
 
     // ---- per-predicate postings -> sorted distinct TSIDs -----------------
     // scratch: match buffer + sort ping-pong (3 x total_rows u64)

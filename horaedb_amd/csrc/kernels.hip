@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include "hx_device.h"
 #include "snappy_emit.h"
+#include "ba_pages.h"
 
 namespace hx {
 
@@ -2730,6 +2731,7 @@ k_decode_delta_i64(const uint8_t* blob, uint8_t* dec,
 #include <cstring>
 #include <cstdlib>
 #include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
 
 namespace hx {
 
@@ -3057,6 +3059,291 @@ k_page_minmax(const uint8_t* __restrict__ src_base,
                 if ((mx & ~SIGN) == 0) mx = 0;      // +0.0
             }
             out[pg] = PageStat{has ? mn : 0, has ? mx : 0, has ? 1ull : 0ull};
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Kernel 1f: PLAIN BYTE_ARRAY page images of a Binary value
+// column, the write side's twin of k_ba_offsets. Input is one handle per
+// source row (off << 20 | len relative to src, already in output order) and
+// optionally group_start[n_out + 1]: output row i is the concatenation of
+// source rows [group_start[i], group_start[i + 1]) under one length prefix
+// (BytesMergeOperator::merge); without it output row i is source row i. The
+// bytes equal hx::ba_build_pages_host (ba_pages.h), whose header states the
+// refusal rules. Three launches:
+//   k_ba_page_sizes   one block per output row group: row_len[i] (or
+//                     BA_ROW_SKIP) and the page's byte count, a u64 block sum
+//   k_ba_page_scan    one block: exclusive scan of the page sizes
+//   k_ba_build_pages  one block per output row group: a wave-shuffle scan of
+//                     4 + len in tiles of 256 rows gives each row its offset
+//                     in the page (LDS, R <= 8192 rows); then each wave takes
+//                     64 rows at a time, row per lane for short rows, the
+//                     whole wave on one row for long ones (sc_copy: up to
+//                     16 B per lane where the two alignments allow it).
+// Nothing outside [src, src + src_size) is read, nothing outside the page's
+// own [page_off[g], page_off[g + 1]) is written; plain vector stores, no
+// atomics but the two counters.
+// ---------------------------------------------------------------------------
+struct BaBuildParams {
+    const uint8_t* src;
+    uint64_t src_size;
+    const uint64_t* handles;       // n_src
+    const uint32_t* group_start;   // n_out + 1, or null
+    uint32_t n_src, n_out, R, n_pages;
+    uint32_t* row_len;             // n_out
+    unsigned long long* page_size; // n_pages
+    unsigned long long* page_off;  // n_pages + 1
+    uint8_t* out;                  // page_off[n_pages] bytes
+    unsigned long long* counts;    // [0] errors, [1] rows over the value cap
+};
+
+// rows below both bounds are copied by their own lane (unmeasured split)
+#define BA_LANE_MAX_BYTES 256u
+#define BA_LANE_MAX_PARTS 8u
+
+__global__ void __launch_bounds__(256)
+k_ba_page_sizes(BaBuildParams B) {
+    __shared__ unsigned long long wsum[4];
+    unsigned long long n_err = 0, n_cap = 0;
+    for (uint32_t pg = blockIdx.x; pg < B.n_pages; pg += gridDim.x) {
+        const uint64_t row0 = (uint64_t)pg * B.R;
+        const uint64_t row1 = row0 + B.R < B.n_out ? row0 + B.R : B.n_out;
+        unsigned long long sum = 0;
+        for (uint64_t i = row0 + threadIdx.x; i < row1; i += blockDim.x) {
+            const uint64_t a = B.group_start ? B.group_start[i] : i;
+            const uint64_t b = B.group_start ? B.group_start[i + 1] : i + 1;
+            bool skip = false;
+            uint64_t len_sum = 0;
+            if (a > b || b > B.n_src) {
+                n_err++;
+                skip = true;
+            } else {
+                for (uint64_t j = a; j < b; j++) {
+                    const uint64_t h = B.handles[j];
+                    const uint64_t off = h >> BA_LEN_BITS;
+                    const uint64_t len = h & BA_LEN_MASK;
+                    if (off > B.src_size || len > B.src_size - off) {
+                        n_err++;
+                        skip = true;
+                    }
+                    len_sum += len;
+                }
+                if (!skip && len_sum > BA_MAX_VALUE_LEN) {
+                    n_cap++;
+                    skip = true;
+                }
+            }
+            B.row_len[i] = skip ? BA_ROW_SKIP : (uint32_t)len_sum;
+            sum += 4 + (skip ? 0 : len_sum);
+        }
+        for (int m = 32; m > 0; m >>= 1) sum += __shfl_xor(sum, m);
+        __syncthreads();   // the previous page's wsum is consumed
+        if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = sum;
+        __syncthreads();
+        if (threadIdx.x == 0)
+            B.page_size[pg] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    }
+    if (n_err) atomicAdd(&B.counts[0], n_err);
+    if (n_cap) atomicAdd(&B.counts[1], n_cap);
+}
+
+// offs[i] = sum(size[0, i)), offs[n] = the total; k_snappy_scan's pattern.
+__global__ void __launch_bounds__(256)
+k_ba_page_scan(const unsigned long long* __restrict__ size, uint32_t n,
+               unsigned long long* __restrict__ offs) {
+    __shared__ unsigned long long part[256];
+    const uint32_t t = threadIdx.x;
+    unsigned long long carry = 0;
+    for (uint32_t base = 0; base < n; base += 256) {
+        const uint32_t i = base + t;
+        const unsigned long long own = i < n ? size[i] : 0;
+        part[t] = own;
+        __syncthreads();
+        for (uint32_t st = 1; st < 256; st <<= 1) {
+            const unsigned long long add = t >= st ? part[t - st] : 0;
+            __syncthreads();
+            part[t] += add;
+            __syncthreads();
+        }
+        if (i < n) offs[i] = carry + part[t] - own;
+        carry += part[255];
+        __syncthreads();
+    }
+    if (t == 0) offs[n] = carry;
+}
+
+// One lane copies len bytes: 8- or 4-byte words where d and s agree modulo
+// the width, bytes up to d's alignment and at the end.
+__device__ __forceinline__ void ba_lane_copy(uint8_t* d, const uint8_t* s,
+                                             uint32_t len) {
+    const uint32_t diff = uint32_t((uintptr_t)d ^ (uintptr_t)s);
+    uint32_t i = 0;
+    if ((diff & 7u) == 0 && len >= 8) {
+        for (; i < len && ((uintptr_t)(d + i) & 7u); i++) d[i] = s[i];
+        for (; i + 8 <= len; i += 8)
+            *(uint64_t*)(d + i) = *(const uint64_t*)(s + i);
+    } else if ((diff & 3u) == 0 && len >= 4) {
+        for (; i < len && ((uintptr_t)(d + i) & 3u); i++) d[i] = s[i];
+        for (; i + 4 <= len; i += 4)
+            *(uint32_t*)(d + i) = *(const uint32_t*)(s + i);
+    }
+    for (; i < len; i++) d[i] = s[i];
+}
+
+__global__ void __launch_bounds__(256)
+k_ba_build_pages(BaBuildParams B) {
+    __shared__ uint32_t roff[BA_MAX_ROW_GROUP];   // row's offset in the page
+    __shared__ uint32_t wtot[4];
+    const uint32_t t = threadIdx.x;
+    const uint32_t lane = t & 63u, wave = t >> 6;
+    for (uint32_t pg = blockIdx.x; pg < B.n_pages; pg += gridDim.x) {
+        const unsigned long long p0 = B.page_off[pg];
+        const unsigned long long p_len = B.page_off[pg + 1] - p0;
+        if (p_len > BA_MAX_PAGE_BYTES) continue;   // block-uniform
+        const uint64_t row0 = (uint64_t)pg * B.R;
+        const uint32_t rows = uint32_t(
+            (row0 + B.R < B.n_out ? row0 + B.R : B.n_out) - row0);
+        uint8_t* page = B.out + p0;
+
+        // offsets: inclusive wave scan by shuffles, wave totals through LDS,
+        // a carry from tile to tile (p_len fits 31 bits, so u32 holds)
+        uint32_t carry = 0;
+        for (uint32_t base = 0; base < rows; base += 256) {
+            const uint32_t r = base + t;
+            uint32_t v = 0;
+            if (r < rows) {
+                const uint32_t rl = B.row_len[row0 + r];
+                v = 4u + ((rl & BA_ROW_SKIP) ? 0u : rl);
+            }
+            uint32_t incl = v;
+            for (uint32_t d = 1; d < 64; d <<= 1) {
+                const uint32_t x = __shfl_up(incl, d);
+                if (lane >= d) incl += x;
+            }
+            __syncthreads();   // the previous tile's wtot is consumed
+            if (lane == 63) wtot[wave] = incl;
+            __syncthreads();
+            uint32_t wbase = 0, tile = 0;
+            for (uint32_t w = 0; w < 4; w++) {
+                if (w < wave) wbase += wtot[w];
+                tile += wtot[w];
+            }
+            if (r < rows) roff[r] = carry + wbase + incl - v;
+            carry += tile;
+        }
+        __syncthreads();
+
+        // copy: each wave takes 64 rows at a time
+        for (uint32_t c0 = wave * 64u; c0 < rows; c0 += 256u) {
+            const uint32_t r = c0 + lane;
+            uint32_t len = 0, a = 0, b = 0, o = 0;
+            bool live = false;
+            if (r < rows) {
+                const uint32_t rl = B.row_len[row0 + r];
+                o = roff[r];
+                live = !(rl & BA_ROW_SKIP);
+                len = live ? rl : 0u;
+                // the slot must hold the row; always true for sizes that
+                // came from k_ba_page_sizes over the same arrays
+                if ((unsigned long long)o + 4u + len > p_len) {
+                    live = false;
+                } else {
+                    uint8_t* d = page + o;
+                    if (((uintptr_t)d & 3u) == 0) {
+                        *(uint32_t*)d = len;
+                    } else {
+                        d[0] = uint8_t(len);
+                        d[1] = uint8_t(len >> 8);
+                        d[2] = uint8_t(len >> 16);
+                        d[3] = uint8_t(len >> 24);
+                    }
+                }
+                a = B.group_start ? B.group_start[row0 + r]
+                                  : uint32_t(row0 + r);
+                b = B.group_start ? B.group_start[row0 + r + 1] : a + 1u;
+                if (len == 0) live = false;
+            }
+            const bool own = live && len < BA_LANE_MAX_BYTES &&
+                             b - a <= BA_LANE_MAX_PARTS;
+            if (own) {
+                uint8_t* d = page + o + 4u;
+                uint32_t pos = 0;
+                for (uint32_t j = a; j < b; j++) {
+                    const uint64_t h = B.handles[j];
+                    const uint64_t off = h >> BA_LEN_BITS;
+                    const uint32_t l = uint32_t(h & BA_LEN_MASK);
+                    if (off > B.src_size || l > B.src_size - off ||
+                        l > len - pos)
+                        break;
+                    ba_lane_copy(d + pos, B.src + off, l);
+                    pos += l;
+                }
+            }
+            unsigned long long coop = __ballot(live && !own);
+            while (coop) {
+                const int k = __ffsll(coop) - 1;
+                coop &= coop - 1ull;
+                const uint32_t ka = __shfl(a, k), kb = __shfl(b, k);
+                const uint32_t klen = __shfl(len, k);
+                uint8_t* d = page + __shfl(o, k) + 4u;
+                uint32_t pos = 0;
+                for (uint32_t j = ka; j < kb; j++) {
+                    const uint64_t h = B.handles[j];   // wave-uniform
+                    const uint64_t off = h >> BA_LEN_BITS;
+                    const uint32_t l = uint32_t(h & BA_LEN_MASK);
+                    if (off > B.src_size || l > B.src_size - off ||
+                        l > klen - pos)
+                        break;
+                    sc_copy(d + pos, B.src + off, l, lane, 64);
+                    pos += l;
+                }
+            }
+        }
+        __syncthreads();   // roff is rewritten by the next page
+    }
+}
+
+// Append compaction, behind the sort: equal-PK runs of the sorted rows.
+// flag[i] = 1 where row i opens a run.
+__global__ void __launch_bounds__(256)
+k_group_flags(const unsigned long long* __restrict__ series,
+              const unsigned long long* __restrict__ ts, uint32_t n,
+              uint32_t* __restrict__ flag) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
+         i += blockDim.x * gridDim.x)
+        flag[i] = (i == 0 || series[i] != series[i - 1] ||
+                   ts[i] != ts[i - 1]) ? 1u : 0u;
+}
+
+// rank[i] = exclusive scan of flag. Run g opens at row group_start[g]; its
+// series, ts and (seq_key given) the sequence of its FIRST row, the smallest
+// of the run, go to the head columns. group_start[n_out] = n and *n_out are
+// written by the last row's thread.
+__global__ void __launch_bounds__(256)
+k_group_heads(const uint32_t* __restrict__ flag,
+              const uint32_t* __restrict__ rank,
+              const unsigned long long* __restrict__ series,
+              const unsigned long long* __restrict__ ts,
+              const unsigned long long* __restrict__ seq_key,
+              const uint32_t* __restrict__ perm, uint32_t n,
+              uint32_t* __restrict__ group_start,
+              unsigned long long* __restrict__ head_series,
+              unsigned long long* __restrict__ head_ts,
+              unsigned long long* __restrict__ head_seq,
+              unsigned long long* __restrict__ n_out) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
+         i += blockDim.x * gridDim.x) {
+        const uint32_t g = rank[i];
+        if (flag[i]) {
+            group_start[g] = i;
+            head_series[g] = series[i];
+            head_ts[g] = ts[i];
+            if (seq_key) head_seq[g] = seq_key[perm[i]] >> 32;
+        }
+        if (i == n - 1) {
+            group_start[g + flag[i]] = n;
+            *n_out = g + flag[i];
         }
     }
 }
@@ -3472,6 +3759,101 @@ hipError_t launch_unique_u64(hipStream_t s, const uint64_t* in,
     uint32_t work = (uint32_t)std::min<unsigned long long>(n, 0x7FFFFFFF);
     hipLaunchKernelGGL(k_unique_u64, dim3(grid_for(work, 256)), dim3(256), 0,
                        s, in, n, out, cursor);
+    return hipGetLastError();
+}
+
+hipError_t launch_ba_page_sizes(hipStream_t s, uint64_t src_size,
+                                const uint64_t* handles,
+                                const uint32_t* group_start, uint32_t n_src,
+                                uint32_t n_out, uint32_t row_group,
+                                uint32_t* row_len,
+                                unsigned long long* page_size,
+                                unsigned long long* page_off,
+                                unsigned long long* counts) {
+    if (row_group == 0 || row_group > BA_MAX_ROW_GROUP)
+        return hipErrorInvalidValue;
+    const uint32_t n_pages = (uint32_t)ba_n_pages(n_out, row_group);
+    BaBuildParams B{};
+    B.src_size = src_size;
+    B.handles = handles;
+    B.group_start = group_start;
+    B.n_src = n_src;
+    B.n_out = n_out;
+    B.R = row_group;
+    B.n_pages = n_pages;
+    B.row_len = row_len;
+    B.page_size = page_size;
+    B.page_off = page_off;
+    B.counts = counts;
+    if (n_pages)
+        hipLaunchKernelGGL(k_ba_page_sizes,
+                           dim3(n_pages > 65536u ? 65536u : n_pages),
+                           dim3(256), 0, s, B);
+    hipLaunchKernelGGL(k_ba_page_scan, dim3(1), dim3(256), 0, s, page_size,
+                       n_pages, page_off);
+    return hipGetLastError();
+}
+
+hipError_t launch_ba_build_pages(hipStream_t s, const uint8_t* src,
+                                 uint64_t src_size, const uint64_t* handles,
+                                 const uint32_t* group_start, uint32_t n_src,
+                                 uint32_t n_out, uint32_t row_group,
+                                 const uint32_t* row_len,
+                                 const unsigned long long* page_off,
+                                 uint8_t* out) {
+    if (row_group == 0 || row_group > BA_MAX_ROW_GROUP)
+        return hipErrorInvalidValue;
+    const uint32_t n_pages = (uint32_t)ba_n_pages(n_out, row_group);
+    if (n_pages == 0) return hipSuccess;
+    BaBuildParams B{};
+    B.src = src;
+    B.src_size = src_size;
+    B.handles = handles;
+    B.group_start = group_start;
+    B.n_src = n_src;
+    B.n_out = n_out;
+    B.R = row_group;
+    B.n_pages = n_pages;
+    B.row_len = const_cast<uint32_t*>(row_len);
+    B.page_off = const_cast<unsigned long long*>(page_off);
+    B.out = out;
+    hipLaunchKernelGGL(k_ba_build_pages,
+                       dim3(n_pages > 65536u ? 65536u : n_pages), dim3(256),
+                       0, s, B);
+    return hipGetLastError();
+}
+
+hipError_t launch_group_heads(hipStream_t s, const unsigned long long* series,
+                              const unsigned long long* ts,
+                              const unsigned long long* seq_key,
+                              const uint32_t* perm, uint32_t n,
+                              uint32_t* flag, uint32_t* rank,
+                              uint32_t* group_start,
+                              unsigned long long* head_series,
+                              unsigned long long* head_ts,
+                              unsigned long long* head_seq,
+                              unsigned long long* n_out, void** d_temp,
+                              size_t* temp_bytes) {
+    if (n == 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_group_flags, dim3(grid_for(n, 256)), dim3(256), 0, s,
+                       series, ts, n, flag);
+    size_t need = 0;
+    hipError_t e = rocprim::exclusive_scan(nullptr, need, flag, rank, 0u,
+                                           (size_t)n, rocprim::plus<uint32_t>(),
+                                           s);
+    if (e != hipSuccess) return e;
+    if (need > *temp_bytes) {
+        if (*d_temp) (void)hipFree(*d_temp);
+        e = hipMalloc(d_temp, need);
+        if (e != hipSuccess) { *temp_bytes = 0; *d_temp = nullptr; return e; }
+        *temp_bytes = need;
+    }
+    e = rocprim::exclusive_scan(*d_temp, *temp_bytes, flag, rank, 0u,
+                                (size_t)n, rocprim::plus<uint32_t>(), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_group_heads, dim3(grid_for(n, 256)), dim3(256), 0, s,
+                       flag, rank, series, ts, seq_key, perm, n, group_start,
+                       head_series, head_ts, head_seq, n_out);
     return hipGetLastError();
 }
 

@@ -518,7 +518,7 @@ std::string write_table_sst(const std::string& path, const WriterCol* cols,
         const WriterCol& wc = cols[c];
         if (wc.physical != 2 && wc.physical != 5 && wc.physical != 6)
             return fail("write_table_sst: unsupported physical type");
-        if (wc.physical == 6 && !wc.offsets)
+        if (wc.physical == 6 && !wc.offsets && !ready)
             return fail("write_table_sst: BYTE_ARRAY needs offsets");
     }
     if (fwrite("PAR1", 1, 4, f) != 4) return fail("write failed");
@@ -543,26 +543,63 @@ std::string write_table_sst(const std::string& path, const WriterCol* cols,
             const uint8_t* body = nullptr;
             size_t body_len = 0;
             if (wc.physical == 6) {
-                const uint8_t* bytes = (const uint8_t*)wc.data;
-                payload.clear();
-                m.has_stats = true;
-                std::string mn, mx;
-                for (int64_t r = base; r < base + rows; r++) {
-                    int64_t b0 = wc.offsets[r], b1 = wc.offsets[r + 1];
-                    if (b1 < b0) return fail("write_table_sst: bad offsets");
-                    uint32_t len = (uint32_t)(b1 - b0);
-                    payload.insert(payload.end(), (const uint8_t*)&len,
-                                   (const uint8_t*)&len + 4);
-                    payload.insert(payload.end(), bytes + b0, bytes + b1);
-                    std::string v((const char*)bytes + b0, (size_t)len);
-                    if (r == base || v < mn) mn = v;
-                    if (r == base || v > mx) mx = v;
+                // a ready entry IS the uncompressed page image (kernel 1f);
+                // otherwise the image is built here from (bytes, offsets)
+                const PagePayload* r6 =
+                    ready && ready[g * n_cols + c].ptr
+                        ? &ready[g * n_cols + c] : nullptr;
+                if (r6) {
+                    body = r6->ptr;
+                    body_len = r6->len;
+                } else {
+                    if (!wc.offsets)
+                        return fail("write_table_sst: BYTE_ARRAY needs "
+                                    "offsets");
+                    const uint8_t* bytes = (const uint8_t*)wc.data;
+                    payload.clear();
+                    for (int64_t r = base; r < base + rows; r++) {
+                        int64_t b0 = wc.offsets[r], b1 = wc.offsets[r + 1];
+                        if (b1 < b0 || b1 - b0 > 0x7FFFFFFF)
+                            return fail("write_table_sst: bad offsets");
+                        uint32_t len = (uint32_t)(b1 - b0);
+                        payload.insert(payload.end(), (const uint8_t*)&len,
+                                       (const uint8_t*)&len + 4);
+                        payload.insert(payload.end(), bytes + b0, bytes + b1);
+                    }
+                    body = payload.data();
+                    body_len = payload.size();
                 }
-                if (mn.size() > 64 || mx.size() > 64) m.has_stats = false;
-                m.mn = mn;
-                m.mx = mx;
-                body = payload.data();
-                body_len = payload.size();
+                if (body_len > 0x7FFFFFFFull)
+                    return fail("write_table_sst: BYTE_ARRAY page image "
+                                "above INT32_MAX bytes");
+                // statistics by walking the image, whoever built it
+                const uint8_t *mn = nullptr, *mx = nullptr;
+                uint32_t mn_len = 0, mx_len = 0;
+                auto less = [](const uint8_t* a, uint32_t al,
+                               const uint8_t* b, uint32_t bl) {
+                    const int k = std::memcmp(a, b, al < bl ? al : bl);
+                    return k < 0 || (k == 0 && al < bl);
+                };
+                size_t pos = 0;
+                for (int64_t r = 0; r < rows; r++) {
+                    if (pos + 4 > body_len)
+                        return fail("write_table_sst: short BYTE_ARRAY page");
+                    uint32_t len;
+                    std::memcpy(&len, body + pos, 4);
+                    pos += 4;
+                    if (len > body_len - pos)
+                        return fail("write_table_sst: short BYTE_ARRAY page");
+                    const uint8_t* v = body + pos;
+                    if (r == 0 || less(v, len, mn, mn_len)) mn = v, mn_len = len;
+                    if (r == 0 || less(mx, mx_len, v, len)) mx = v, mx_len = len;
+                    pos += len;
+                }
+                if (pos != body_len)
+                    return fail("write_table_sst: BYTE_ARRAY page longer "
+                                "than its rows");
+                m.has_stats = mn_len <= 64 && mx_len <= 64;
+                m.mn.assign((const char*)mn, mn_len);
+                m.mx.assign((const char*)mx, mx_len);
             } else {
                 if (!column_present(wc.data, ready, g * n_cols + c, codec))
                     return fail("write_table_sst: column neither given nor "
@@ -653,6 +690,30 @@ std::string write_metric_sst_seqs(const std::string& path,
         {"__reserved__", 2, 14, zeros.data(), nullptr},
     };
     return write_table_sst(path, cols, 5, n, row_group, codec, ready);
+}
+
+std::string write_metric_sst_bytes(const std::string& path,
+                                   const uint64_t* series, const int64_t* ts,
+                                   const uint8_t* bytes,
+                                   const int64_t* offsets,
+                                   const uint64_t* seqs, uint64_t seq,
+                                   int64_t n, int64_t row_group,
+                                   const PagePayload* ready) {
+    if (n <= 0) return "write_metric_sst_bytes: no rows";
+    std::vector<uint64_t> zeros(n, 0), seq_col;
+    if (!seqs) {
+        seq_col.assign(n, seq);
+        seqs = seq_col.data();
+    }
+    WriterCol cols[5] = {
+        {"series_id", 2, 14, series, nullptr},
+        {"timestamp", 2, -1, ts, nullptr},
+        {"value", 6, -1, bytes, offsets},
+        {"__seq__", 2, 14, seqs, nullptr},
+        {"__reserved__", 2, 14, zeros.data(), nullptr},
+    };
+    // pages stay uncompressed: staging reads no Snappy byte pages
+    return write_table_sst(path, cols, 5, n, row_group, 0, ready);
 }
 
 }  // namespace hx

@@ -20,7 +20,10 @@ namespace hx {
 // streams made elsewhere (kernel 1e): entry [row group * n_cols + column],
 // ptr null = absent, the writer compresses that page itself. A ready stream
 // must be the twin's bytes for the page, so the file does not depend on who
-// compressed it. BYTE_ARRAY chunks stay uncompressed.
+// compressed it. BYTE_ARRAY chunks stay uncompressed under every codec; a
+// ready entry for one IS its uncompressed page image (u32 length + bytes per
+// row, kernel 1f or hx::ba_build_pages_host), taken whatever the codec, and
+// its statistics are always computed by the writer from the image.
 // A ready entry may bring the chunk's statistics too (k_page_minmax, the raw
 // 8 bytes of min and max as minmax over the column would give them); a
 // column whose every page comes ready WITH statistics may be passed as a
@@ -96,5 +99,25 @@ std::string write_metric_sst_seqs(const std::string& path,
                                   int64_t n, int64_t row_group,
                                   int32_t codec = 0,
                                   const PagePayload* ready = nullptr);
+
+// Binary-value form of the metric writer (the schema behind
+// BytesMergeOperator / UpdateMode::Append): series_id (INT64/UINT_64),
+// timestamp (INT64), value (BYTE_ARRAY, no converted type), __seq__,
+// __reserved__, all REQUIRED — the names and types pyarrow-written Binary SSTs
+// of a store carry, so both kinds mix in one store. seqs: per-row __seq__, or
+// NULL for the constant `seq`. The value column comes as (bytes,
+// offsets[n + 1]) or, per row group, as a ready entry [row group * 5 + 2]
+// holding the UNCOMPRESSED page image (u32 length + bytes per row; kernel 1f
+// or hx::ba_build_pages_host); with every page ready, bytes and offsets may
+// be null. Pages are never compressed. Statistics are computed by walking the
+// page image (lexicographic min/max, omitted above 64 B), so the file is a
+// pure function of the rows whichever route built the pages.
+std::string write_metric_sst_bytes(const std::string& path,
+                                   const uint64_t* series, const int64_t* ts,
+                                   const uint8_t* bytes,
+                                   const int64_t* offsets,
+                                   const uint64_t* seqs, uint64_t seq,
+                                   int64_t n, int64_t row_group,
+                                   const PagePayload* ready = nullptr);
 
 }  // namespace hx

@@ -140,6 +140,19 @@ def _load():
         C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32,
         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
         C.POINTER(C.c_uint64)]
+    lib.hx_write_bytes.argtypes = [
+        C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int64), C.c_void_p,
+        C.POINTER(C.c_int64), C.c_int64, C.c_int32, C.POINTER(C.c_uint64)]
+    lib.hx_write_sst_bytes.argtypes = [
+        C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int64), C.c_void_p,
+        C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.c_uint64, C.c_int64,
+        C.c_int64]
+    for f in (lib.hx_debug_ba_pages, lib.hx_debug_ba_pages_host):
+        f.argtypes = [
+            C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32,
+            C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32,
+            C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64,
+            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.hx_schema.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t),
                               C.POINTER(C.c_size_t)]
     lib.hx_catalog_size.argtypes = [C.c_void_p, C.POINTER(C.c_size_t)]
@@ -314,7 +327,7 @@ class Store:
         npk = C.c_size_t()
         _check(_lib.hx_schema(self._h, C.cast(C.byref(out), C.c_void_p),
                               C.byref(n), C.byref(npk)))
-        tnames = {0: "u64", 1: "i64", 2: "f64"}
+        tnames = {0: "u64", 1: "i64", 2: "f64", 3: "binary"}
         cols = [{"name": out[i].name.decode(),
                  "type": tnames[out[i].col_type],
                  "primary_key": bool(out[i].is_primary_key),
@@ -483,6 +496,21 @@ class Store:
             1 if enable_check else 0, C.byref(out)))
         return out.value
 
+    def write_bytes(self, series, ts, values, enable_check=True):
+        """ColumnarStorage::write for a Binary value column (hx_write_bytes):
+        values is a sequence of bytes objects, each below 2^20 bytes.
+        Returns the new file's sequence."""
+        series = np.ascontiguousarray(series, dtype=np.uint64)
+        ts_a = np.ascontiguousarray(ts, dtype=np.int64)
+        blob, offs = _bytes_col(values, len(series))
+        out = C.c_uint64()
+        _check(_lib.hx_write_bytes(
+            self._h, series.ctypes.data_as(C.POINTER(C.c_uint64)),
+            ts_a.ctypes.data_as(C.POINTER(C.c_int64)), blob.ctypes.data,
+            offs.ctypes.data_as(C.POINTER(C.c_int64)), len(series),
+            1 if enable_check else 0, C.byref(out)))
+        return out.value
+
     def compact_files(self, input_seqs, devices=None):
         """General compaction of an EXPLICIT input set (executor
         Task{inputs}, keep_builtin): dedups among the named files only;
@@ -598,6 +626,88 @@ def write_sst_native(path, series, ts, value, seq, row_group=8192):
         path.encode(), series.ctypes.data_as(C.POINTER(C.c_uint64)),
         ts.ctypes.data_as(C.POINTER(C.c_int64)),
         value.ctypes.data_as(C.POINTER(C.c_double)), seq, n, row_group))
+
+
+def _bytes_col(values, n):
+    """sequence of n bytes objects -> (uint8 blob, int64 offsets[n + 1])."""
+    values = [v if isinstance(v, (bytes, bytearray)) else bytes(v)
+              for v in values]
+    if len(values) != n:
+        raise ValueError("values: one bytes object per row")
+    offs = np.zeros(n + 1, dtype=np.int64)
+    if n:
+        offs[1:] = np.cumsum([len(v) for v in values], dtype=np.int64)
+    blob = np.frombuffer(b"".join(values) or b"\0", dtype=np.uint8)
+    return blob, offs
+
+
+def write_sst_native_bytes(path, series, ts, values, seq, seqs=None,
+                           row_group=8192):
+    """GPU-free writer of one Binary-value SST (hx_write_sst_bytes), rows in
+    the order given. seqs: per-row __seq__ values, or None for the constant
+    seq."""
+    series = np.ascontiguousarray(series, dtype=np.uint64)
+    ts = np.ascontiguousarray(ts, dtype=np.int64)
+    n = len(series)
+    blob, offs = _bytes_col(values, n)
+    sq = None if seqs is None else np.ascontiguousarray(seqs, dtype=np.uint64)
+    _check(_lib.hx_write_sst_bytes(
+        path.encode(), series.ctypes.data_as(C.POINTER(C.c_uint64)),
+        ts.ctypes.data_as(C.POINTER(C.c_int64)), blob.ctypes.data,
+        offs.ctypes.data_as(C.POINTER(C.c_int64)),
+        None if sq is None else sq.ctypes.data_as(C.POINTER(C.c_uint64)),
+        int(seq), n, row_group))
+
+
+def _ba_pages_call(fn, src, handles, group_start, n_out, row_group, build):
+    raw = bytes(src)
+    src_a = np.frombuffer(raw or b"\0", dtype=np.uint8)
+    handles = np.ascontiguousarray(handles, dtype=np.uint64)
+    n_src = len(handles)
+    gs = None if group_start is None else \
+        np.ascontiguousarray(group_start, dtype=np.uint32)
+    if n_out is None:
+        n_out = n_src if gs is None else len(gs) - 1
+    n_pages = (n_out + row_group - 1) // row_group
+    page_off = np.zeros(n_pages + 1, dtype=np.uint64)
+    errs, over = C.c_uint64(), C.c_uint64()
+    hp = handles.ctypes.data_as(C.POINTER(C.c_uint64)) if n_src else None
+    gp = None if gs is None else gs.ctypes.data_as(C.POINTER(C.c_uint32))
+    pp = page_off.ctypes.data_as(C.POINTER(C.c_uint64))
+    # sizes first (host twin: no GPU), so `out` is exactly the image
+    _check(_lib.hx_debug_ba_pages_host(
+        src_a.ctypes.data, len(raw), hp, n_src, gp, n_out, row_group, pp,
+        None, 0, C.byref(errs), C.byref(over)))
+    pages = None
+    if build:
+        total = int(page_off[-1])
+        out = np.full(max(total, 1), 0xA5, dtype=np.uint8)
+        _check(fn(src_a.ctypes.data, len(raw), hp, n_src, gp, n_out,
+                  row_group, pp, out.ctypes.data, total, C.byref(errs),
+                  C.byref(over)))
+        pages = [out[int(page_off[g]):int(page_off[g + 1])].tobytes()
+                 for g in range(n_pages)]
+    return pages, errs.value, over.value
+
+
+def ba_pages_host(src, handles, group_start=None, n_out=None,
+                  row_group=8192, build=True):
+    """The host twin of kernel 1f (test hook hx_debug_ba_pages_host; no GPU
+    needed). src: bytes; handles: uint64 (off << 20 | len) per source row in
+    output order; group_start: n_out + 1 source-row bounds, or None. Returns
+    (pages, n_errors, n_over_cap): pages[g] is output row group g's PLAIN
+    BYTE_ARRAY page image, refused rows written as empty values."""
+    return _ba_pages_call(_lib.hx_debug_ba_pages_host, src, handles,
+                          group_start, n_out, row_group, build)
+
+
+def ba_pages_device(src, handles, group_start=None, n_out=None,
+                    row_group=8192, build=True):
+    """Kernel 1f through the test hook hx_debug_ba_pages (needs a GPU): the
+    production launches over device buffers of exactly the stated sizes.
+    Arguments and result as ba_pages_host."""
+    return _ba_pages_call(_lib.hx_debug_ba_pages, src, handles, group_start,
+                          n_out, row_group, build)
 
 
 def _validity_bits(valid, n):

@@ -346,6 +346,52 @@ hx_status hx_write_sst_codec(const char* path, const uint64_t* series,
                              uint64_t seq, int64_t n_rows, int64_t row_group,
                              int32_t codec);
 
+/* ---- Binary value stores: the write side ------------------------------
+ * The schema behind BytesMergeOperator / UpdateMode::Append: series_id,
+ * timestamp, value (BYTE_ARRAY), __seq__, __reserved__, all REQUIRED, pages
+ * PLAIN and uncompressed. THE VALUE LIMIT: a value is at most 2^20 - 1
+ * bytes, because the reader describes a value by a handle with 20 length
+ * bits (k_ba_offsets refuses a longer one at read time). Every writer
+ * enforces it: a longer value given to hx_write_bytes / hx_write_sst_bytes
+ * returns HX_ERR_INVALID; an Append compaction (hx_compact,
+ * hx_compact_files) whose concatenation of one equal-PK group would exceed
+ * it returns HX_ERR_UNSUPPORTED; hx_index_write refuses such a tag key or
+ * value (HX_ERR_INVALID). A row group whose value page would exceed
+ * INT32_MAX bytes returns HX_ERR_UNSUPPORTED (multi-page chunks are not
+ * written). Every refusal comes before anything is written or unlinked.
+ *
+ * hx_compact / hx_compact_files on such a store: Overwrite keeps the
+ * winner's bytes (last wins). Append turns each equal-PK run of the inputs,
+ * in ascending (__seq__, file row) order, into ONE row holding the
+ * concatenation; hx_compact gives it the new file's sequence,
+ * hx_compact_files the sequence of the run's FIRST row, the smallest
+ * (BytesMergeOperator keeps element 0 of every non-value column,
+ * operator.rs:99-102). Value bytes stay on the device until they leave as
+ * finished page images. */
+
+/* ColumnarStorage::write for the Binary schema: row i's value is
+ * bytes[offsets[i], offsets[i + 1]). Segment check, stable PK sort (equal
+ * PKs keep batch order), file id = sequence, catalog add. On an empty store
+ * the store becomes a Binary store; on an f64 store HX_ERR_SCHEMA; with
+ * hx_set_nullable_values(1) or a write codec set, HX_ERR_UNSUPPORTED.
+ * hx_write / hx_write_nullable on a Binary store return HX_ERR_UNSUPPORTED.
+ * From 65536 rows with a device the sort (the ingest sort hx_write uses)
+ * and the page images are made on the GPU; the file is the same either way.
+ * Unlike hx_write, which sorts on the host when a HIP call of its device
+ * sort fails, a HIP failure on this route returns HX_ERR_HIP and writes
+ * nothing. */
+hx_status hx_write_bytes(hx_handle*, const uint64_t* series, const int64_t* ts,
+                         const uint8_t* bytes, const int64_t* offsets,
+                         int64_t n_rows, int32_t enable_check,
+                         uint64_t* out_seq);
+
+/* GPU-free writer of one Binary-value SST, rows in the order given; seqs:
+ * per-row __seq__ values, or NULL for the constant seq. */
+hx_status hx_write_sst_bytes(const char* path, const uint64_t* series,
+                             const int64_t* ts, const uint8_t* bytes,
+                             const int64_t* offsets, const uint64_t* seqs,
+                             uint64_t seq, int64_t n_rows, int64_t row_group);
+
 /* ---- inverted index (RFC docs/rfcs/20240827-metric-engine.md:86-137) ----
  * The reference's planned index tables (its metric_engine index module is
  * an uncompiled skeleton; semantics pinned by the RFC): an `index` table
