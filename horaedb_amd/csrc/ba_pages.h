@@ -137,4 +137,89 @@ inline void ba_build_pages_host(const uint8_t* src, uint64_t src_size,
     }
 }
 
+// ---------------------------------------------------------------------------
+// Host twin of kernel 1g (k_ba_page_minmax): the footer statistics of the
+// page images above, one BaPageStat per page, without a walk of whole values.
+//
+// The writer's rule (write_table_sst's walk of an image): lexicographic order
+// on unsigned bytes, a proper prefix is smaller; the chunk carries min/max
+// only when both are at most BA_STAT_MAX bytes long.
+//
+// Here a value v is looked at through K(v), its first min(len, 65) bytes,
+// under the same order, and no more than 65 bytes of any value are read.
+// That gives the writer's verdict and bytes:
+//   - the true min m has len <= 64: then K(m) = m, and no other value v has
+//     K(v) < m without v < m. A key of 65 bytes is longer than m, so it is no
+//     prefix of m, and it sorts below m only through a byte inside both,
+//     which v has too. So the K-min is m (or a value equal to it).
+//   - len(m) > 64: every v >= m. If a v with len(v) <= 64 had K(v) = v <=
+//     K(m), then v <= K(m) <= m (a prefix is smaller), so v = m, a
+//     contradiction. The K-min winner is longer than 64 bytes and the
+//     statistics are omitted either way.
+//   - the true max M has len <= 64: K(M) = M, and every K(v) <= v <= M (a
+//     prefix is never larger), so the K-max is M.
+//   - len(M) > 64: K(M) has 65 bytes. A K-max winner w with len(w) <= 64
+//     would be its own key, w = K(w) >= K(M); being shorter than K(M) it
+//     can only be larger through a byte inside both, which M has too, so
+//     w > M: a contradiction. The winner is longer than 64 bytes and the
+//     statistics are omitted either way.
+// has = 0 (no min/max for the chunk) leaves the lengths 0 and the bytes zero;
+// unused bytes of min/max are zero, so twin and kernel compare as memory.
+// A refused row (BA_ROW_SKIP) is the empty value its page carries. A row that
+// would not fit its page (never true for sizes from the size pass over the
+// same arrays) is left out.
+// ---------------------------------------------------------------------------
+constexpr uint32_t BA_STAT_MAX = 64;
+
+struct BaPageStat {
+    uint32_t has, min_len, max_len;
+    uint8_t min[BA_STAT_MAX];
+    uint8_t max[BA_STAT_MAX];
+};
+static_assert(sizeof(BaPageStat) == 140, "BaPageStat is 140 bytes");
+
+// a < b on keys (pointer, key length <= 65)
+inline bool ba_key_less(const uint8_t* a, uint32_t al, const uint8_t* b,
+                        uint32_t bl) {
+    const uint32_t n = al < bl ? al : bl;
+    const int k = n ? std::memcmp(a, b, n) : 0;
+    return k < 0 || (k == 0 && al < bl);
+}
+
+inline void ba_page_minmax_host(const uint8_t* image, const uint64_t* page_off,
+                                const uint32_t* row_len, uint64_t n_out,
+                                uint64_t R, BaPageStat* out) {
+    const uint64_t n_pages = ba_n_pages(n_out, R);
+    for (uint64_t g = 0; g < n_pages; g++) {
+        BaPageStat st;
+        std::memset(&st, 0, sizeof st);
+        const uint64_t p_len = page_off[g + 1] - page_off[g];
+        const uint8_t* page = image + page_off[g];
+        const uint8_t *mn = nullptr, *mx = nullptr;
+        uint32_t mn_k = 0, mx_k = 0;
+        bool any = false;
+        uint64_t pos = 0;
+        const uint64_t r1 = (g + 1) * R < n_out ? (g + 1) * R : n_out;
+        for (uint64_t i = g * R; i < r1 && p_len <= BA_MAX_PAGE_BYTES; i++) {
+            const uint32_t len = (row_len[i] & BA_ROW_SKIP) ? 0u : row_len[i];
+            const uint64_t o = pos;
+            pos += 4ull + len;
+            if (o + 4ull + len > p_len) continue;
+            const uint8_t* v = page + o + 4;
+            const uint32_t kl = len < BA_STAT_MAX + 1 ? len : BA_STAT_MAX + 1;
+            if (!any || ba_key_less(v, kl, mn, mn_k)) mn = v, mn_k = kl;
+            if (!any || ba_key_less(mx, mx_k, v, kl)) mx = v, mx_k = kl;
+            any = true;
+        }
+        if (any && mn_k <= BA_STAT_MAX && mx_k <= BA_STAT_MAX) {
+            st.has = 1;
+            st.min_len = mn_k;
+            st.max_len = mx_k;
+            if (mn_k) std::memcpy(st.min, mn, mn_k);
+            if (mx_k) std::memcpy(st.max, mx, mx_k);
+        }
+        out[g] = st;
+    }
+}
+
 }  // namespace hx

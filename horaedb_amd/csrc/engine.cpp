@@ -101,6 +101,8 @@ struct hx_handle {
     int32_t write_codec = 0;             // writer setting: page codec of
                                          // every SST this handle writes
                                          // (hx_set_write_codec)
+    int32_t bytes_write_codec = 0;       // the same for the Binary writers
+                                         // (hx_set_bytes_write_codec)
     std::vector<CatSst> ssts;            // ascending seq
     std::vector<hx_sst_desc> find_out;   // scratch for hx_find_ssts
 };
@@ -302,6 +304,19 @@ extern "C" hx_status hx_set_write_codec(hx_handle* h, int32_t codec) {
     return HX_OK;
 }
 
+// The Binary writers' codec (hx_write_bytes, and hx_compact /
+// hx_compact_files on a Binary store); hx_set_write_codec keeps its meaning
+// and its refusals. 0 launches and writes exactly what it always did.
+extern "C" hx_status hx_set_bytes_write_codec(hx_handle* h, int32_t codec) {
+    if (!h || (codec != HX_CODEC_NONE && codec != HX_CODEC_SNAPPY))
+        return fail(HX_ERR_INVALID, "bytes write codec: 0 none / 1 snappy");
+    if (codec != HX_CODEC_NONE && !h->bytes_value && !h->ssts.empty())
+        return fail(HX_ERR_UNSUPPORTED,
+                    "a bytes write codec needs a Binary value column");
+    h->bytes_write_codec = codec;
+    return HX_OK;
+}
+
 // TimeRange::overlaps (types.rs:125-127): [start,end) vs file [min,max]
 static bool overlaps(const CatSst& s, hx_time_range r) {
     return s.ts_min < r.end && s.ts_max >= r.start;
@@ -356,10 +371,16 @@ struct DevPlan {
     std::vector<hx::DeltaPageDesc> delta_pages;
     std::vector<hx::BaPageDesc> ba_pages;   // byte-value stores: handle walk
     std::vector<hx::SnappyPageDesc> snappy_pages;
+    // Snappy pages of a Binary value column, decoded into the blob's tail
+    std::vector<hx::SnappyPageDesc> snappy_ba_pages;
     std::vector<hx::ExpandPageDesc> expand_pages;  // OPTIONAL PLAIN bodies
     std::vector<hx::RleDictPageDesc> rledict_pages;
     std::vector<hx::CopyDesc> copies;
-    size_t blob_bytes = 0;
+    size_t blob_bytes = 0;   // staged (uploaded) bytes of d_blob
+    // d_blob's whole extent: [blob_bytes, blob_span) is the decoded tail of
+    // Snappy byte-value pages, never uploaded, written by ensure_decoded with
+    // dec's lifetime and rewrite rules. Value handles address [0, blob_span).
+    size_t blob_span = 0;
     size_t dec_bytes = 0;
     int64_t rows_scanned = 0;
     // stored Snappy pages read in place from the blob (hx_get_decode_stats)
@@ -383,6 +404,7 @@ struct DevPlan {
     hx::DeltaPageDesc* d_delta = nullptr;
     hx::BaPageDesc* d_ba = nullptr;
     hx::SnappyPageDesc* d_snappy = nullptr;
+    hx::SnappyPageDesc* d_snappy_ba = nullptr;
     hx::ExpandPageDesc* d_expand = nullptr;
     hx::RleDictPageDesc* d_rledict = nullptr;
     hx::CopyDesc* d_copies = nullptr;
@@ -567,7 +589,8 @@ static size_t layout_jobs(hx_prepared* P, DevPlan& plan,
 // and none looks at its neighbours, so the order carries no meaning.
 static hx_status stage_chunks(DevPlan& plan, const std::vector<PageJob>& jobs,
                               std::vector<hx::ChunkResult>& results,
-                              std::atomic<size_t>& dec) {
+                              std::atomic<size_t>& dec,
+                              std::atomic<size_t>& tail) {
     const unsigned n_threads = std::min<unsigned>(
         16, std::max(1u, std::thread::hardware_concurrency()));
     std::vector<hx::StagedPages> bundles(n_threads);
@@ -605,7 +628,7 @@ static hx_status stage_chunks(DevPlan& plan, const std::vector<PageJob>& jobs,
                         *j.cr, j.role.col, j.role.bytes_value);
                 }
                 s = hx::stage_chunk(tmp.data(), *j.cr, j.role, slot, dec, out,
-                                    results[i]);
+                                    results[i], &tail);
                 if (!s.ok()) s.msg = cat->path + ": " + s.msg;
             }
             if (!s.ok()) {
@@ -628,6 +651,7 @@ static hx_status stage_chunks(DevPlan& plan, const std::vector<PageJob>& jobs,
     };
     for (const hx::StagedPages& b : bundles) {
         append(plan.snappy_pages, b.snappy);
+        append(plan.snappy_ba_pages, b.snappy_ba);
         append(plan.expand_pages, b.expand);
         append(plan.delta_pages, b.delta);
         append(plan.rledict_pages, b.rledict);
@@ -662,7 +686,8 @@ static hx_status upload_plan(DevPlan& plan) {
     HIP_TRY(hipSetDevice(plan.device));
     if (!plan.stream) HIP_TRY(hipStreamCreate(&plan.stream));
     if (plan.blob_bytes) {
-        HIP_TRY(hipMalloc((void**)&plan.d_blob, plan.blob_bytes + 64));
+        // the tail behind blob_bytes is decode output, not uploaded
+        HIP_TRY(hipMalloc((void**)&plan.d_blob, plan.blob_span + 64));
         HIP_TRY(hipMemcpyAsync(plan.d_blob, plan.h_blob, plan.blob_bytes,
                                hipMemcpyHostToDevice, plan.stream));
     }
@@ -695,6 +720,7 @@ static hx_status upload_plan(DevPlan& plan) {
     HIP_TRY(upload(plan.d_delta, plan.delta_pages));
     HIP_TRY(upload(plan.d_ba, plan.ba_pages));
     HIP_TRY(upload(plan.d_snappy, plan.snappy_pages));
+    HIP_TRY(upload(plan.d_snappy_ba, plan.snappy_ba_pages));
     HIP_TRY(upload(plan.d_expand, plan.expand_pages));
     HIP_TRY(upload(plan.d_rledict, plan.rledict_pages));
     HIP_TRY(upload(plan.d_copies, plan.copies));
@@ -728,9 +754,17 @@ static hx_status stage_device(hx_prepared* P, DevPlan& plan,
         }
     }
     std::vector<hx::ChunkResult> results(jobs.size());
-    hx_status st = stage_chunks(plan, jobs, results, dec);
+    // blob_bytes is a multiple of 64 (layout_jobs), so every tail piece is
+    std::atomic<size_t> tail{plan.blob_bytes};
+    hx_status st = stage_chunks(plan, jobs, results, dec, tail);
     if (st != HX_OK) return st;
     plan.dec_bytes = dec.load();
+    plan.blob_span = tail.load();
+    if (P->h->bytes_value && uint64_t(plan.blob_span) >= (1ull << 44))
+        return fail(HX_ERR_UNSUPPORTED,
+                    "Binary value store: staged and decoded value pages of "
+                    "one plan exceed 2^44 bytes (a value handle has 44 "
+                    "offset bits)");
     slice_and_order(plan, results);
     st = upload_plan(plan);
     // staging buffer no longer needed once resident in HBM (frees up to
@@ -932,7 +966,8 @@ extern "C" void hx_prepared_free(hx_prepared* P) {
                         (void*)plan.d_ssts, (void*)plan.d_clusters,
                         (void*)plan.d_members, (void*)plan.d_delta,
                         (void*)plan.d_ba,
-                        (void*)plan.d_snappy, (void*)plan.d_expand,
+                        (void*)plan.d_snappy, (void*)plan.d_snappy_ba,
+                        (void*)plan.d_expand,
                         (void*)plan.d_rledict,
                         (void*)plan.d_copies, (void*)plan.t_slab,
                         (void*)plan.t_bstore, (void*)plan.d_counters,
@@ -1096,6 +1131,14 @@ hx_status ensure_decoded(DevPlan& plan, hipStream_t s) {
                                         plan.d_delta,
                                         (uint32_t)plan.delta_pages.size(),
                                         plan.d_counters + 1));
+    if (!plan.snappy_ba_pages.empty())
+        // Snappy pages of a Binary value column go to the blob's tail: the
+        // blob is source and decode base at once, the ranges are disjoint
+        // (streams below blob_bytes, output at and above it)
+        HIP_TRY(hx::launch_snappy(s, plan.d_blob, plan.d_blob,
+                                  plan.d_snappy_ba,
+                                  (uint32_t)plan.snappy_ba_pages.size(),
+                                  plan.d_counters + 1));
     if (!plan.ba_pages.empty())
         // byte-value stores: walk the PLAIN BYTE_ARRAY length prefixes of
         // the value pages into per-row handles (off << 20 | len) in dec
@@ -1940,8 +1983,11 @@ extern "C" hx_status hx_get_decode_stats(hx_prepared* P, hx_decode_stats* out) {
     for (const DevPlan& plan : P->plans) {
         s.pages_in_place += plan.pages_in_place;
         s.bytes_in_place += plan.bytes_in_place;
-        s.pages_decoded += plan.snappy_pages.size();
+        s.pages_decoded += plan.snappy_pages.size() +
+                           plan.snappy_ba_pages.size();
         for (const auto& sp : plan.snappy_pages)
+            s.bytes_decoded_out += sp.uncomp_len;
+        for (const auto& sp : plan.snappy_ba_pages)
             s.bytes_decoded_out += sp.uncomp_len;
     }
     *out = s;
@@ -1985,9 +2031,10 @@ extern "C" hx_status hx_debug_page_levels(
     role.col = col;
     role.bytes_value = cat.bytes_value;
     std::atomic<size_t> dec{0};
+    std::atomic<size_t> tail{hx::align64(slot_mem.size())};
     hx::StagedPages pages;
     hx::ChunkResult res;
-    s = hx::stage_chunk(tmp.data(), cr, role, slot, dec, pages, res);
+    s = hx::stage_chunk(tmp.data(), cr, role, slot, dec, pages, res, &tail);
     if (!s.ok()) return fail(s.st, cat.path + ": " + s.msg);
     *n_rows = cr.num_values;
     *n_valid = res.n_valid;
@@ -2832,6 +2879,10 @@ static hx_status write_batch(hx_handle* h, const uint64_t* series,
         return fail(HX_ERR_UNSUPPORTED,
                     "the store's value column is Binary: write it with "
                     "hx_write_bytes");
+    if (h->bytes_write_codec)
+        return fail(HX_ERR_UNSUPPORTED,
+                    "a bytes write codec is set (hx_set_bytes_write_codec): "
+                    "the handle writes a Binary value column");
     if (enable_check) {
         // segment-crossing check (storage.rs:309-316). The reference uses
         // Rust truncating division on start/seg vs (end-1)/seg, where end
@@ -3315,6 +3366,149 @@ std::vector<hx::PagePayload> ba_ready(const uint64_t* page_off,
     return r;
 }
 
+// Snappy streams and footer statistics of a value column's page images, as
+// the writer takes them under codec Snappy (PagePayload: stream, ulen,
+// ba_stat), whoever made them.
+struct BaStreams {
+    std::vector<uint8_t> bytes;          // the streams, back to back
+    std::vector<uint32_t> lens;          // per page
+    std::vector<hx::BaPageStat> stats;   // per page
+    size_t d2h_bytes = 0;                // device route: what came back
+    float stats_ms = 0, compress_ms = 0; // device route under HX_DEBUG
+};
+
+// the host route: hx::ba_page_minmax_host and hx::snappy_compress_host
+void ba_streams_host(const uint8_t* image, const uint64_t* page_off,
+                     uint32_t n_pages, const uint32_t* row_len,
+                     uint64_t n_out, BaStreams& out) {
+    out.stats.resize(n_pages);
+    out.lens.resize(n_pages);
+    hx::ba_page_minmax_host(image, page_off, row_len, n_out, kRowGroup,
+                            out.stats.data());
+    out.bytes.clear();
+    for (uint32_t g = 0; g < n_pages; g++) {
+        const size_t n = size_t(page_off[g + 1] - page_off[g]);
+        const size_t at = out.bytes.size();
+        out.bytes.resize(at + size_t(hx::snappy_max_compressed(n)));
+        const size_t got = hx::snappy_compress_host(
+            image + page_off[g], n, out.bytes.data() + at,
+            out.bytes.size() - at);
+        out.lens[g] = uint32_t(got);
+        out.bytes.resize(at + got);
+    }
+}
+
+// the value column's entries of a ready table (n_pages * 5 entries)
+void ba_ready_streams(std::vector<hx::PagePayload>& ready,
+                      const uint64_t* page_off, uint32_t n_pages,
+                      const BaStreams& st) {
+    ready.resize(size_t(n_pages) * 5, hx::PagePayload{});
+    size_t at = 0;
+    for (uint32_t g = 0; g < n_pages; g++) {
+        hx::PagePayload& r = ready[size_t(g) * 5 + 2];
+        r = hx::PagePayload{};
+        r.ptr = st.bytes.data() + at;
+        r.len = st.lens[g];
+        r.ulen = uint32_t(page_off[g + 1] - page_off[g]);
+        r.ba_stat = &st.stats[g];
+        at += st.lens[g];
+    }
+}
+
+// The device route: kernel 1g over the image kernel 1f left in HBM, kernel 1e
+// with one SnappyCompDesc per page image (slots at Snappy's bound; n and
+// dst_cap are u32, which a page of at most INT32_MAX bytes fits), the
+// scan-and-pack pass, then lengths + statistics and ONE contiguous copy of
+// the streams. d_page_off / d_row_len as the size pass left them; page_off
+// its host copy (every page already checked against BA_MAX_PAGE_BYTES).
+hipError_t compress_ba_pages_device(hipStream_t s, const uint8_t* d_image,
+                                    const uint64_t* page_off,
+                                    uint32_t n_pages,
+                                    const unsigned long long* d_page_off,
+                                    const uint32_t* d_row_len, uint32_t n_out,
+                                    bool timed, BaStreams& out) {
+    std::vector<hx::SnappyCompDesc> descs(n_pages);
+    size_t slot_bytes = 0;
+    for (uint32_t g = 0; g < n_pages; g++) {
+        hx::SnappyCompDesc& d = descs[g];
+        d.src_off = page_off[g];
+        d.n = uint32_t(page_off[g + 1] - page_off[g]);
+        d.dst_cap = uint32_t(hx::snappy_max_compressed(d.n));
+        d.dst_off = slot_bytes;
+        slot_bytes = align64(slot_bytes + d.dst_cap);
+    }
+    out.bytes.clear();
+    out.lens.assign(n_pages, 0);
+    out.stats.assign(n_pages, hx::BaPageStat{});
+    out.d2h_bytes = 0;
+    if (n_pages == 0) return hipSuccess;
+    const size_t desc_bytes = align64(size_t(n_pages) * sizeof(descs[0]));
+    const size_t off_bytes = align64(size_t(n_pages) * 8);
+    // read back first, in one copy: lengths, error count, statistics
+    const size_t len_bytes = (size_t(n_pages) * 4 + 7) & ~size_t(7);
+    const size_t stat_bytes = size_t(n_pages) * sizeof(hx::BaPageStat);
+    const size_t back_bytes = len_bytes + 8 + stat_bytes;
+    uint8_t* dev = nullptr;
+    hipError_t e = hipMalloc((void**)&dev, 2 * slot_bytes + desc_bytes +
+                                               off_bytes + back_bytes);
+    if (e != hipSuccess) return e;
+    std::unique_ptr<void, void (*)(void*)> guard(
+        dev, [](void* q) { (void)hipFree(q); });
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    struct EvGuard {
+        hipEvent_t* e;
+        ~EvGuard() {
+            for (int i = 0; i < 3; i++)
+                if (e[i]) (void)hipEventDestroy(e[i]);
+        }
+    } ev_guard{ev};
+    uint8_t* d_slots = dev;
+    uint8_t* d_packed = dev + slot_bytes;
+    auto* d_descs = (hx::SnappyCompDesc*)(d_packed + slot_bytes);
+    auto* d_offs = (unsigned long long*)((uint8_t*)d_descs + desc_bytes);
+    uint32_t* d_lens = (uint32_t*)((uint8_t*)d_offs + off_bytes);
+    unsigned long long* d_err =
+        (unsigned long long*)((uint8_t*)d_lens + len_bytes);
+    hx::BaPageStat* d_stats = (hx::BaPageStat*)(d_err + 1);
+#define BS_TRY(x) do { e = (x); if (e != hipSuccess) return e; } while (0)
+    if (timed)
+        for (auto& v : ev) BS_TRY(hipEventCreate(&v));
+    BS_TRY(hipMemcpyAsync(d_descs, descs.data(),
+                          size_t(n_pages) * sizeof(descs[0]),
+                          hipMemcpyHostToDevice, s));
+    BS_TRY(hipMemsetAsync(d_err, 0, 8, s));
+    if (timed) BS_TRY(hipEventRecord(ev[0], s));
+    BS_TRY(hx::launch_ba_page_minmax(s, d_image, d_page_off, d_row_len, n_out,
+                                     (uint32_t)kRowGroup, d_stats));
+    if (timed) BS_TRY(hipEventRecord(ev[1], s));
+    BS_TRY(hx::launch_snappy_compress(s, d_image, d_slots, d_descs, n_pages,
+                                      d_lens, d_err));
+    BS_TRY(hx::launch_snappy_pack(s, d_slots, d_descs, n_pages, d_lens,
+                                  d_offs, d_packed));
+    if (timed) BS_TRY(hipEventRecord(ev[2], s));
+    std::vector<uint64_t> back((back_bytes + 7) / 8);
+    BS_TRY(hipMemcpyAsync(back.data(), d_lens, back_bytes,
+                          hipMemcpyDeviceToHost, s));
+    BS_TRY(hipStreamSynchronize(s));
+    if (back[len_bytes / 8] != 0) return hipErrorUnknown;
+    std::memcpy(out.lens.data(), back.data(), size_t(n_pages) * 4);
+    std::memcpy(out.stats.data(), (const uint8_t*)back.data() + len_bytes + 8,
+                stat_bytes);
+    size_t total = 0;
+    for (uint32_t g = 0; g < n_pages; g++) total += out.lens[g];
+    out.bytes.resize(total);
+    BS_TRY(hipMemcpyAsync(out.bytes.data(), d_packed, total,
+                          hipMemcpyDeviceToHost, s));
+    BS_TRY(hipStreamSynchronize(s));
+    if (timed) {
+        BS_TRY(hipEventElapsedTime(&out.stats_ms, ev[0], ev[1]));
+        BS_TRY(hipEventElapsedTime(&out.compress_ms, ev[1], ev[2]));
+    }
+#undef BS_TRY
+    out.d2h_bytes = back_bytes + total;
+    return hipSuccess;
+}
+
 // (bytes, offsets) batches of hx_write_bytes / hx_write_sst_bytes
 hx_status check_value_offsets(const int64_t* offsets, int64_t n) {
     if (offsets[0] < 0) return fail(HX_ERR_INVALID, "negative offset");
@@ -3341,8 +3535,18 @@ extern "C" hx_status hx_write_sst_bytes(const char* path,
                                         const int64_t* offsets,
                                         const uint64_t* seqs, uint64_t seq,
                                         int64_t n_rows, int64_t row_group) {
+    return hx_write_sst_bytes_codec(path, series, ts, bytes, offsets, seqs,
+                                    seq, n_rows, row_group, HX_CODEC_NONE);
+}
+
+extern "C" hx_status hx_write_sst_bytes_codec(
+    const char* path, const uint64_t* series, const int64_t* ts,
+    const uint8_t* bytes, const int64_t* offsets, const uint64_t* seqs,
+    uint64_t seq, int64_t n_rows, int64_t row_group, int32_t codec) {
     if (!path || !series || !ts || !offsets || n_rows <= 0 || row_group <= 0)
         return fail(HX_ERR_INVALID, "bad argument");
+    if (codec != HX_CODEC_NONE && codec != HX_CODEC_SNAPPY)
+        return fail(HX_ERR_INVALID, "write codec: 0 none / 1 snappy");
     hx_status st = check_value_offsets(offsets, n_rows);
     if (st != HX_OK) return st;
     if (!bytes && offsets[n_rows] != offsets[0])
@@ -3356,9 +3560,12 @@ extern "C" hx_status hx_write_sst_bytes(const char* path,
     }
     st = check_page_sizes(page_off.data(), page_off.size() - 1);
     if (st != HX_OK) return st;
+    // the writer builds each page image from (bytes, offsets), the bytes
+    // hx::ba_build_pages_host gives, and under Snappy compresses it with
+    // hx::snappy_compress_host
     std::string err = hx::write_metric_sst_bytes(path, series, ts, bytes,
                                                  offsets, seqs, seq, n_rows,
-                                                 row_group);
+                                                 row_group, nullptr, codec);
     if (!err.empty()) return fail(HX_ERR_IO, err);
     return HX_OK;
 }
@@ -3433,15 +3640,86 @@ extern "C" hx_status hx_debug_ba_pages(
     return HX_OK;
 }
 
+// argument check shared by hx_debug_ba_page_minmax and its host form
+static bool ba_minmax_args_ok(const uint8_t* image, const uint64_t* page_off,
+                              const uint32_t* row_len, uint32_t n_out,
+                              uint32_t row_group, const uint8_t* stats_out) {
+    if (!page_off || !row_len || !stats_out || n_out == 0 ||
+        row_group == 0 || row_group > hx::BA_MAX_ROW_GROUP ||
+        page_off[0] != 0)
+        return false;
+    const uint64_t n_pages = hx::ba_n_pages(n_out, row_group);
+    for (uint64_t g = 0; g < n_pages; g++) {
+        uint64_t sum = 0;
+        const uint64_t r1 = std::min<uint64_t>((g + 1) * row_group, n_out);
+        for (uint64_t i = g * row_group; i < r1; i++)
+            sum += 4ull + ((row_len[i] & hx::BA_ROW_SKIP) ? 0u : row_len[i]);
+        if (page_off[g + 1] < page_off[g] ||
+            page_off[g + 1] - page_off[g] != sum ||
+            sum > hx::BA_MAX_PAGE_BYTES)
+            return false;
+    }
+    return image != nullptr;
+}
+
+extern "C" hx_status hx_debug_ba_page_minmax_host(
+    const uint8_t* image, const uint64_t* page_off, const uint32_t* row_len,
+    uint32_t n_out, uint32_t row_group, uint8_t* stats_out) {
+    if (!ba_minmax_args_ok(image, page_off, row_len, n_out, row_group,
+                           stats_out))
+        return fail(HX_ERR_INVALID, "bad argument");
+    std::vector<hx::BaPageStat> st(hx::ba_n_pages(n_out, row_group));
+    hx::ba_page_minmax_host(image, page_off, row_len, n_out, row_group,
+                            st.data());
+    std::memcpy(stats_out, st.data(), st.size() * sizeof(hx::BaPageStat));
+    return HX_OK;
+}
+
+extern "C" hx_status hx_debug_ba_page_minmax(
+    const uint8_t* image, const uint64_t* page_off, const uint32_t* row_len,
+    uint32_t n_out, uint32_t row_group, uint8_t* stats_out) {
+    if (!ba_minmax_args_ok(image, page_off, row_len, n_out, row_group,
+                           stats_out))
+        return fail(HX_ERR_INVALID, "bad argument");
+    const size_t n_pages = hx::ba_n_pages(n_out, row_group);
+    const size_t total = page_off[n_pages];
+    const size_t st_bytes = n_pages * sizeof(hx::BaPageStat);
+    DevBufs dev;
+    uint8_t* d_image = nullptr;
+    unsigned long long* d_off = nullptr;
+    uint32_t* d_len = nullptr;
+    hx::BaPageStat* d_st = nullptr;
+    HIP_TRY(dev.alloc((void**)&d_image, total));
+    HIP_TRY(dev.alloc((void**)&d_off, (n_pages + 1) * 8));
+    HIP_TRY(dev.alloc((void**)&d_len, size_t(n_out) * 4));
+    HIP_TRY(dev.alloc((void**)&d_st, st_bytes));
+    HIP_TRY(hipMemcpy(d_image, image, total, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_off, page_off, (n_pages + 1) * 8,
+                      hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_len, row_len, size_t(n_out) * 4,
+                      hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(d_st, 0xEE, st_bytes));
+    HIP_TRY(hx::launch_ba_page_minmax(nullptr, d_image, d_off, d_len, n_out,
+                                      row_group, d_st));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(stats_out, d_st, st_bytes, hipMemcpyDeviceToHost));
+    return HX_OK;
+}
+
 // The device route of hx_write_bytes: the ingest sort's permutation (two
 // stable LSD passes, ts then series), the handles gathered by it, kernel 1f
 // over the uploaded value bytes, and ONE copy back: sorted series, sorted ts
-// and the page images, in that order in `host`.
+// and the page images, in that order in `host`. Under codec Snappy (keys and
+// values given) nothing of that comes back: kernel 1g and kernel 1e run over
+// the image, kernel 1e over the sorted series and ts where the gather left
+// them, and the host receives lengths, statistics and streams.
 static hx_status gpu_write_bytes(const uint64_t* series, const int64_t* ts,
                                  const uint8_t* bytes, uint64_t n_bytes,
                                  const std::vector<uint64_t>& handles,
                                  int64_t n, std::vector<uint8_t>& host,
-                                 std::vector<uint64_t>& page_off) {
+                                 std::vector<uint64_t>& page_off,
+                                 DeviceStreams* keys = nullptr,
+                                 BaStreams* values = nullptr) {
     hipStream_t s = nullptr;
     const size_t N = (size_t)n;
     DevBufs dev;
@@ -3491,11 +3769,21 @@ static hx_status gpu_write_bytes(const uint64_t* series, const int64_t* ts,
                                       (uint32_t)N, (uint32_t)N,
                                       (uint32_t)kRowGroup, b.d_row_len,
                                       b.d_words, d_final + key_bytes));
+    page_off.assign(b.page_off.begin(), b.page_off.begin() + b.n_pages + 1);
+    if (keys && values) {
+        HIP_TRY(compress_ba_pages_device(s, d_final + key_bytes,
+                                         page_off.data(), b.n_pages,
+                                         b.d_words, b.d_row_len, (uint32_t)N,
+                                         false, *values));
+        const int64_t col_words[5] = {0, (int64_t)N, -1, -1, -1};
+        HIP_TRY(compress_columns_device(s, d_final, col_words, (uint32_t)N,
+                                        nullptr, *keys));
+        return HX_OK;
+    }
     host.resize(key_bytes + b.total());
     HIP_TRY(hipMemcpyAsync(host.data(), d_final, host.size(),
                            hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    page_off.assign(b.page_off.begin(), b.page_off.begin() + b.n_pages + 1);
     return HX_OK;
 }
 
@@ -3543,9 +3831,15 @@ extern "C" hx_status hx_write_bytes(hx_handle* h, const uint64_t* series,
     std::vector<uint8_t> host;        // sorted series, sorted ts, page images
     std::vector<uint64_t> page_off;
     const size_t N = (size_t)n;
+    const int32_t codec = h->bytes_write_codec;
+    DeviceStreams key_streams;        // codec Snappy, device route
+    BaStreams value_streams;          // codec Snappy, either route
+    bool on_device = false;
     if (n >= (1 << 16) && hip_device_count() > 0) {
+        on_device = codec == HX_CODEC_SNAPPY;
         st = gpu_write_bytes(series, ts, src, n_bytes, handles, n, host,
-                             page_off);
+                             page_off, on_device ? &key_streams : nullptr,
+                             on_device ? &value_streams : nullptr);
         if (st != HX_OK) return st;
     } else {
         std::vector<uint32_t> order(n);
@@ -3575,19 +3869,29 @@ extern "C" hx_status hx_write_bytes(hx_handle* h, const uint64_t* series,
         hx::ba_build_pages_host(src, n_bytes, hs.data(), N, nullptr, N,
                                 kRowGroup, row_len.data(), page_off.data(),
                                 host.data() + 2 * N * 8);
+        if (codec == HX_CODEC_SNAPPY)
+            ba_streams_host(host.data() + 2 * N * 8, page_off.data(),
+                            (uint32_t)n_pages, row_len.data(), N,
+                            value_streams);
     }
     uint64_t max_seq = 0;
     for (const auto& s : h->ssts) max_seq = std::max(max_seq, s.seq);
     const uint64_t new_seq = max_seq + 1;
     std::string out_path = h->store + "/data/" + std::to_string(new_seq) +
                            ".sst";
-    std::vector<hx::PagePayload> ready =
-        ba_ready(page_off.data(), (uint32_t)(page_off.size() - 1),
-                 host.data() + 2 * N * 8);
+    const uint32_t n_pages32 = (uint32_t)(page_off.size() - 1);
+    std::vector<hx::PagePayload> ready;
+    if (codec == HX_CODEC_SNAPPY) {
+        // the key columns' streams (device route), then the value column's
+        if (on_device) ready = key_streams.ready;
+        ba_ready_streams(ready, page_off.data(), n_pages32, value_streams);
+    } else {
+        ready = ba_ready(page_off.data(), n_pages32, host.data() + 2 * N * 8);
+    }
     std::string werr = hx::write_metric_sst_bytes(
-        out_path, (const uint64_t*)host.data(),
-        (const int64_t*)(host.data() + N * 8), nullptr, nullptr, nullptr,
-        new_seq, n, kRowGroup, ready.data());
+        out_path, on_device ? nullptr : (const uint64_t*)host.data(),
+        on_device ? nullptr : (const int64_t*)(host.data() + N * 8), nullptr,
+        nullptr, nullptr, new_seq, n, kRowGroup, ready.data(), codec);
     if (!werr.empty()) return fail(HX_ERR_IO, werr);
     CatSst fresh;
     st = read_file_meta(out_path, new_seq, fresh);
@@ -3740,7 +4044,7 @@ static hx_status compact_rows_bytes(hx_handle* h, hx_prepared* P,
         HIP_TRY(hipEventRecord(ev[0], s));
     }
     BaPageBuilder b;
-    st = b.run(s, plan.blob_bytes, d_handles, d_gs, n, n_out,
+    st = b.run(s, plan.blob_span, d_handles, d_gs, n, n_out,
                (uint32_t)kRowGroup);
     if (st == HX_OK) st = b.verdict();
     if (st != HX_OK) return st;   // nothing written, nothing unlinked
@@ -3748,7 +4052,7 @@ static hx_status compact_rows_bytes(hx_handle* h, hx_prepared* P,
     const size_t key_bytes = n_keys * size_t(n_out) * 8;
     uint8_t* d_final = nullptr;
     HIP_TRY(dev.alloc((void**)&d_final, key_bytes + b.total()));
-    HIP_TRY(hx::launch_ba_build_pages(s, plan.d_blob, plan.blob_bytes,
+    HIP_TRY(hx::launch_ba_build_pages(s, plan.d_blob, plan.blob_span,
                                       d_handles, d_gs, n, n_out,
                                       (uint32_t)kRowGroup, b.d_row_len,
                                       b.d_words, d_final + key_bytes));
@@ -3758,6 +4062,46 @@ static hx_status compact_rows_bytes(hx_handle* h, hx_prepared* P,
         HIP_TRY(hipMemcpyAsync(d_final + k * size_t(n_out) * 8, keys[k],
                                size_t(n_out) * 8, hipMemcpyDeviceToDevice,
                                s));
+    const uint64_t new_seq = max_seq + 1;
+    std::string out_path = h->store + "/data/" + std::to_string(new_seq) +
+                           ".sst";
+    if (h->bytes_write_codec == HX_CODEC_SNAPPY) {
+        // the image stays in HBM: statistics (kernel 1g) and streams (kernel
+        // 1e) of the value pages, streams and statistics of the key columns;
+        // lengths + statistics + one contiguous copy of the streams each
+        BaStreams vs;
+        DeviceStreams ks;
+        HIP_TRY(compress_ba_pages_device(s, d_final + key_bytes,
+                                         b.page_off.data(), b.n_pages,
+                                         b.d_words, b.d_row_len, n_out, timed,
+                                         vs));
+        const int64_t col_words[5] = {
+            0, (int64_t)n_out, -1, keep_seq ? 2 * (int64_t)n_out : -1, -1};
+        HIP_TRY(compress_columns_device(s, d_final, col_words, n_out, nullptr,
+                                        ks));
+        if (timed) {
+            float pages_ms = 0;
+            HIP_TRY(hipEventElapsedTime(&pages_ms, ev[0], ev[1]));
+            size_t stream_bytes = vs.bytes.size();
+            fprintf(stderr,
+                    "[hx] compact_bytes rows=%u out_rows=%u append=%d "
+                    "keep_seq=%d pages=%u codec=snappy pages_ms=%.4f "
+                    "stats_ms=%.4f compress_ms=%.4f value_stream_bytes=%zu "
+                    "image_bytes=%zu decode_ms=%.4f d2h_bytes=%zu\n",
+                    n, n_out, int(append), int(keep_seq), b.n_pages, pages_ms,
+                    vs.stats_ms, vs.compress_ms, stream_bytes,
+                    size_t(b.total()), plan.decode_ms,
+                    vs.d2h_bytes + ks.d2h_bytes +
+                        (size_t(b.n_pages) + 3) * 8 + (append ? 8 : 0) + 8);
+        }
+        std::vector<hx::PagePayload> ready = ks.ready;
+        ba_ready_streams(ready, b.page_off.data(), b.n_pages, vs);
+        std::string werr = hx::write_metric_sst_bytes(
+            out_path, nullptr, nullptr, nullptr, nullptr, nullptr, new_seq,
+            n_out, kRowGroup, ready.data(), HX_CODEC_SNAPPY);
+        if (!werr.empty()) return fail(HX_ERR_IO, werr);
+        return finish_compaction(h, out_path, new_seq, in_set, out_new_seq);
+    }
     std::vector<uint8_t> host(key_bytes + b.total());
     HIP_TRY(hipMemcpyAsync(host.data(), d_final, host.size(),
                            hipMemcpyDeviceToHost, s));
@@ -3767,15 +4111,13 @@ static hx_status compact_rows_bytes(hx_handle* h, hx_prepared* P,
         HIP_TRY(hipEventElapsedTime(&pages_ms, ev[0], ev[1]));
         fprintf(stderr,
                 "[hx] compact_bytes rows=%u out_rows=%u append=%d "
-                "keep_seq=%d pages=%u pages_ms=%.4f d2h_bytes=%zu\n",
+                "keep_seq=%d pages=%u pages_ms=%.4f decode_ms=%.4f "
+                "d2h_bytes=%zu\n",
                 n, n_out, int(append), int(keep_seq), b.n_pages, pages_ms,
-                host.size() + (size_t(b.n_pages) + 3) * 8 +
+                plan.decode_ms, host.size() + (size_t(b.n_pages) + 3) * 8 +
                     (append ? 8 : 0) + 8);
     }
 
-    const uint64_t new_seq = max_seq + 1;
-    std::string out_path = h->store + "/data/" + std::to_string(new_seq) +
-                           ".sst";
     std::vector<hx::PagePayload> ready =
         ba_ready(b.page_off.data(), b.n_pages, host.data() + key_bytes);
     const uint64_t* hk = (const uint64_t*)host.data();

@@ -102,3 +102,22 @@ extern "C" hx_status hx_debug_snappy_compress(
     const uint8_t* pages, const uint64_t* offs, const uint32_t* lens,
     uint32_t n_pages, const uint32_t* src_align, uint8_t* out,
     const uint64_t* out_offs, uint32_t* out_lens, uint64_t* n_errors);
+
+// Test hook (exported, not part of the public C-ABI): run the production
+// launch of kernel 1g (hx::launch_ba_page_minmax, hx_kernels.h; rule and host
+// twin in ba_pages.h) once over a caller-built image on the current device.
+// image: page_off[n_pages] bytes, n_pages = ceil(n_out / row_group);
+// page_off: n_pages + 1 ascending entries from 0; row_len: n_out words as the
+// size pass leaves them (BA_ROW_SKIP = a refused row, an empty value), whose
+// 4 + len per row must add up to each page's size, else HX_ERR_INVALID;
+// row_group <= 8192. stats_out receives n_pages BaPageStat records of 140
+// bytes {u32 has, min_len, max_len; u8 min[64]; u8 max[64]}, pre-filled with
+// 0xEE on the device and copied back whole. Every device buffer is exactly as
+// large as stated here. hx_debug_ba_page_minmax_host is the same over the
+// host twin, no GPU needed.
+extern "C" hx_status hx_debug_ba_page_minmax(
+    const uint8_t* image, const uint64_t* page_off, const uint32_t* row_len,
+    uint32_t n_out, uint32_t row_group, uint8_t* stats_out);
+extern "C" hx_status hx_debug_ba_page_minmax_host(
+    const uint8_t* image, const uint64_t* page_off, const uint32_t* row_len,
+    uint32_t n_out, uint32_t row_group, uint8_t* stats_out);

@@ -2,6 +2,7 @@
 // device code in one TU; no -fgpu-rdc needed).
 #pragma once
 #include <hip/hip_runtime.h>
+#include "ba_pages.h"
 #include "hx_device.h"
 
 namespace hx {
@@ -162,6 +163,14 @@ hipError_t launch_ba_build_pages(hipStream_t s, const uint8_t* src,
                                  const uint32_t* row_len,
                                  const unsigned long long* page_off,
                                  uint8_t* out);
+// Kernel 1g, one workgroup per page of the image kernel 1f built (page_off
+// and row_len as its size pass left them): the chunk's footer statistics by
+// ba_pages.h's 65-byte rule, the bytes of hx::ba_page_minmax_host. out: one
+// BaPageStat per page.
+hipError_t launch_ba_page_minmax(hipStream_t s, const uint8_t* image,
+                                 const unsigned long long* page_off,
+                                 const uint32_t* row_len, uint32_t n_out,
+                                 uint32_t row_group, BaPageStat* out);
 // Equal-PK runs of n sorted rows (n > 0): flag and rank are n words of
 // scratch; group_start gets n_out + 1 entries (room for n + 1), the head
 // columns one entry per run, *n_out the run count. seq_key (may be null):

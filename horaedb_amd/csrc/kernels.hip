@@ -3191,6 +3191,32 @@ __device__ __forceinline__ void ba_lane_copy(uint8_t* d, const uint8_t* s,
     for (; i < len; i++) d[i] = s[i];
 }
 
+// One tile of 256 rows of the page-offset scan kernels 1f and 1g share: v is
+// the thread's row size (4 + len, 0 past the page's rows). Inclusive wave scan
+// by shuffles, wave totals through LDS (wtot, 4 words), a carry from tile to
+// tile (a page fits 31 bits, so u32 holds). Returns the row's offset in the
+// page. Every thread of the block calls it.
+__device__ __forceinline__ uint32_t ba_tile_scan(uint32_t v, uint32_t lane,
+                                                 uint32_t wave, uint32_t* wtot,
+                                                 uint32_t& carry) {
+    uint32_t incl = v;
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+        const uint32_t x = __shfl_up(incl, d);
+        if (lane >= d) incl += x;
+    }
+    __syncthreads();   // the previous tile's wtot is consumed
+    if (lane == 63) wtot[wave] = incl;
+    __syncthreads();
+    uint32_t wbase = 0, tile = 0;
+    for (uint32_t w = 0; w < 4; w++) {
+        if (w < wave) wbase += wtot[w];
+        tile += wtot[w];
+    }
+    const uint32_t o = carry + wbase + incl - v;
+    carry += tile;
+    return o;
+}
+
 __global__ void __launch_bounds__(256)
 k_ba_build_pages(BaBuildParams B) {
     __shared__ uint32_t roff[BA_MAX_ROW_GROUP];   // row's offset in the page
@@ -3206,8 +3232,7 @@ k_ba_build_pages(BaBuildParams B) {
             (row0 + B.R < B.n_out ? row0 + B.R : B.n_out) - row0);
         uint8_t* page = B.out + p0;
 
-        // offsets: inclusive wave scan by shuffles, wave totals through LDS,
-        // a carry from tile to tile (p_len fits 31 bits, so u32 holds)
+        // offsets (ba_tile_scan; p_len fits 31 bits)
         uint32_t carry = 0;
         for (uint32_t base = 0; base < rows; base += 256) {
             const uint32_t r = base + t;
@@ -3216,21 +3241,8 @@ k_ba_build_pages(BaBuildParams B) {
                 const uint32_t rl = B.row_len[row0 + r];
                 v = 4u + ((rl & BA_ROW_SKIP) ? 0u : rl);
             }
-            uint32_t incl = v;
-            for (uint32_t d = 1; d < 64; d <<= 1) {
-                const uint32_t x = __shfl_up(incl, d);
-                if (lane >= d) incl += x;
-            }
-            __syncthreads();   // the previous tile's wtot is consumed
-            if (lane == 63) wtot[wave] = incl;
-            __syncthreads();
-            uint32_t wbase = 0, tile = 0;
-            for (uint32_t w = 0; w < 4; w++) {
-                if (w < wave) wbase += wtot[w];
-                tile += wtot[w];
-            }
-            if (r < rows) roff[r] = carry + wbase + incl - v;
-            carry += tile;
+            const uint32_t o = ba_tile_scan(v, lane, wave, wtot, carry);
+            if (r < rows) roff[r] = o;
         }
         __syncthreads();
 
@@ -3301,6 +3313,158 @@ k_ba_build_pages(BaBuildParams B) {
             }
         }
         __syncthreads();   // roff is rewritten by the next page
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Kernel 1g: footer statistics of the page images kernel 1f
+// built, so the images need not reach the host for them. One workgroup per
+// page; ba_pages.h states the rule (keys of at most 65 bytes decide) and
+// holds the host twin, hx::ba_page_minmax_host. Row offsets come from the
+// build pass's tile scan; each thread folds its rows into a running min and
+// max, kept as (offset of the value in the page, key length, first key word);
+// keys compare as zero-padded big-endian 8-byte words, then by key length.
+// The four waves reduce by shuffles, then through LDS; 64 threads copy the
+// min, 64 the max. Reads stay inside the page's own [page_off[g],
+// page_off[g + 1]): a key word is assembled from the aligned words around it
+// where both lie in the page, from the value's bytes otherwise, and masked to
+// the value's own bytes. Writes only the page's BaPageStat; plain vector
+// stores, no atomics.
+// ---------------------------------------------------------------------------
+struct BaKey {
+    uint32_t off;    // of the value's first byte in the page
+    uint32_t klen;   // min(len, 65)
+    uint64_t w0;     // key word 0
+};
+
+// key word w (bytes [8w, 8w + 8) of the key, zero past klen), big-endian
+__device__ __forceinline__ uint64_t ba_key_word(const uint8_t* page,
+                                                uint32_t p_len, uint32_t off,
+                                                uint32_t klen, uint32_t w) {
+    if (klen <= 8u * w) return 0;
+    const uint32_t n = klen - 8u * w < 8u ? klen - 8u * w : 8u;
+    const uint8_t* p = page + off + 8u * w;
+    const uint32_t mis = uint32_t((uintptr_t)p & 7u);
+    const uint8_t* a = p - mis;
+    uint64_t v;
+    if (a >= page && a + (mis ? 16u : 8u) <= page + p_len) {
+        v = *(const uint64_t*)a;
+        if (mis)
+            v = (v >> (mis * 8u)) |
+                (*(const uint64_t*)(a + 8) << (64u - mis * 8u));
+    } else {
+        v = 0;
+        for (uint32_t b = 0; b < n; b++) v |= (uint64_t)p[b] << (8u * b);
+    }
+    if (n < 8u) v &= (1ull << (8u * n)) - 1ull;
+    return __builtin_bswap64(v);
+}
+
+__device__ __forceinline__ bool ba_key_lt(const uint8_t* page, uint32_t p_len,
+                                          const BaKey& a, const BaKey& b) {
+    if (a.w0 != b.w0) return a.w0 < b.w0;
+    const uint32_t top = a.klen > b.klen ? a.klen : b.klen;
+    for (uint32_t w = 1; 8u * w < top; w++) {
+        const uint64_t x = ba_key_word(page, p_len, a.off, a.klen, w);
+        const uint64_t y = ba_key_word(page, p_len, b.off, b.klen, w);
+        if (x != y) return x < y;
+    }
+    return a.klen < b.klen;
+}
+
+__device__ __forceinline__ BaKey ba_key_shfl_xor(const BaKey& k, int m) {
+    BaKey o;
+    o.off = __shfl_xor(k.off, m);
+    o.klen = __shfl_xor(k.klen, m);
+    o.w0 = __shfl_xor(k.w0, m);
+    return o;
+}
+
+__global__ void __launch_bounds__(256)
+k_ba_page_minmax(const uint8_t* __restrict__ image,
+                 const unsigned long long* __restrict__ page_off,
+                 const uint32_t* __restrict__ row_len, uint32_t n_out,
+                 uint32_t R, uint32_t n_pages, BaPageStat* __restrict__ out) {
+    __shared__ uint32_t wtot[4];
+    __shared__ BaKey wmin[4], wmax[4];
+    __shared__ uint32_t wany[4];
+    const uint32_t t = threadIdx.x;
+    const uint32_t lane = t & 63u, wave = t >> 6;
+    for (uint32_t pg = blockIdx.x; pg < n_pages; pg += gridDim.x) {
+        const unsigned long long p0 = page_off[pg];
+        const unsigned long long p_len64 = page_off[pg + 1] - p0;
+        const uint64_t row0 = (uint64_t)pg * R;
+        const uint32_t rows = uint32_t(
+            (row0 + R < n_out ? row0 + R : n_out) - row0);
+        const bool page_ok = p_len64 <= BA_MAX_PAGE_BYTES;   // block-uniform
+        const uint32_t p_len = page_ok ? (uint32_t)p_len64 : 0u;
+        const uint8_t* page = image + p0;
+        BaKey mn{0, 0, 0}, mx{0, 0, 0};
+        bool any = false;
+        uint32_t carry = 0;
+        for (uint32_t base = 0; page_ok && base < rows; base += 256) {
+            const uint32_t r = base + t;
+            uint32_t v = 0, len = 0;
+            if (r < rows) {
+                const uint32_t rl = row_len[row0 + r];
+                len = (rl & BA_ROW_SKIP) ? 0u : rl;
+                v = 4u + len;
+            }
+            const uint32_t o = ba_tile_scan(v, lane, wave, wtot, carry);
+            if (r < rows && (unsigned long long)o + v <= p_len) {
+                BaKey k;
+                k.off = o + 4u;
+                k.klen = len < BA_STAT_MAX + 1u ? len : BA_STAT_MAX + 1u;
+                k.w0 = ba_key_word(page, p_len, k.off, k.klen, 0);
+                if (!any || ba_key_lt(page, p_len, k, mn)) mn = k;
+                if (!any || ba_key_lt(page, p_len, mx, k)) mx = k;
+                any = true;
+            }
+        }
+        // across the wave, then the four waves
+        for (int m = 32; m > 0; m >>= 1) {
+            const BaKey omn = ba_key_shfl_xor(mn, m);
+            const BaKey omx = ba_key_shfl_xor(mx, m);
+            const bool oany = __shfl_xor((int)any, m) != 0;
+            if (oany) {
+                if (!any || ba_key_lt(page, p_len, omn, mn)) mn = omn;
+                if (!any || ba_key_lt(page, p_len, mx, omx)) mx = omx;
+                any = true;
+            }
+        }
+        __syncthreads();   // the previous page's wmin / wmax are consumed
+        if (lane == 0) {
+            wmin[wave] = mn;
+            wmax[wave] = mx;
+            wany[wave] = any ? 1u : 0u;
+        }
+        __syncthreads();
+        // every thread folds the four entries the same way
+        bool f_any = false;
+        BaKey f_mn{0, 0, 0}, f_mx{0, 0, 0};
+        for (uint32_t w = 0; w < 4; w++) {
+            if (!wany[w]) continue;
+            const BaKey a = wmin[w], b = wmax[w];
+            if (!f_any || ba_key_lt(page, p_len, a, f_mn)) f_mn = a;
+            if (!f_any || ba_key_lt(page, p_len, f_mx, b)) f_mx = b;
+            f_any = true;
+        }
+        const bool has = f_any && f_mn.klen <= BA_STAT_MAX &&
+                         f_mx.klen <= BA_STAT_MAX;
+        BaPageStat* st = out + pg;
+        if (t == 0) {
+            st->has = has ? 1u : 0u;
+            st->min_len = has ? f_mn.klen : 0u;
+            st->max_len = has ? f_mx.klen : 0u;
+        }
+        if (t < 2u * BA_STAT_MAX) {
+            const bool is_max = t >= BA_STAT_MAX;
+            const uint32_t i = is_max ? t - BA_STAT_MAX : t;
+            const BaKey& k = is_max ? f_mx : f_mn;
+            const uint8_t b = (has && i < k.klen) ? page[k.off + i]
+                                                  : (uint8_t)0;
+            (is_max ? st->max : st->min)[i] = b;
+        }
     }
 }
 
@@ -3820,6 +3984,21 @@ hipError_t launch_ba_build_pages(hipStream_t s, const uint8_t* src,
     hipLaunchKernelGGL(k_ba_build_pages,
                        dim3(n_pages > 65536u ? 65536u : n_pages), dim3(256),
                        0, s, B);
+    return hipGetLastError();
+}
+
+hipError_t launch_ba_page_minmax(hipStream_t s, const uint8_t* image,
+                                 const unsigned long long* page_off,
+                                 const uint32_t* row_len, uint32_t n_out,
+                                 uint32_t row_group, BaPageStat* out) {
+    if (row_group == 0 || row_group > BA_MAX_ROW_GROUP)
+        return hipErrorInvalidValue;
+    const uint32_t n_pages = (uint32_t)ba_n_pages(n_out, row_group);
+    if (n_pages == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_ba_page_minmax,
+                       dim3(n_pages > 65536u ? 65536u : n_pages), dim3(256),
+                       0, s, image, page_off, row_len, n_out, row_group,
+                       n_pages, out);
     return hipGetLastError();
 }
 

@@ -232,15 +232,16 @@ struct PageWriter {
     PageWriter(int32_t codec_, const PagePayload* ready_, int32_t n_cols_)
         : codec(codec_), ready(ready_), n_cols(n_cols_), prev(n_cols_) {}
 
-    // false on a failed write; m gets sizes, codec and data_page_offset
-    bool write(FILE* f, int64_t g, int32_t c, bool compressible,
+    // false on a failed write; m gets sizes, codec and data_page_offset.
+    // snappy: this page is written as a Snappy stream. With a ready stream
+    // body may be null (body_len still the uncompressed size).
+    bool write(FILE* f, int64_t g, int32_t c, bool snappy,
                int32_t n_values, const uint8_t* head, size_t head_len,
                const uint8_t* body, size_t body_len, int64_t& off,
                ChunkMeta& m) {
         const size_t payload = head_len + body_len;
         const uint8_t* out = nullptr;
         size_t out_len = payload;
-        const bool snappy = codec == 1 && compressible;
         if (snappy) {
             const PagePayload* r = ready ? &ready[g * n_cols + c] : nullptr;
             if (r && r->ptr) {
@@ -402,7 +403,7 @@ std::string write_metric_sst(const std::string& path, const uint64_t* series,
                                                m.mn, m.mx);
                     break;
             }
-            if (!pw.write(f, g, c, true, (int32_t)rows, nullptr, 0,
+            if (!pw.write(f, g, c, codec == 1, (int32_t)rows, nullptr, 0,
                           (const uint8_t*)data[c], size_t(rows) * 8, off, m))
                 return fail("write failed");
         }
@@ -483,7 +484,7 @@ std::string write_metric_sst_nullable(const std::string& path,
                                                m.mn, m.mx);
                     break;
             }
-            if (!pw.write(f, g, c, true, (int32_t)rows, levels.data(),
+            if (!pw.write(f, g, c, codec == 1, (int32_t)rows, levels.data(),
                           c == 2 ? levels.size() : 0,
                           (const uint8_t*)data[c], size_t(body), off, m))
                 return fail("write failed");
@@ -504,9 +505,11 @@ std::string write_metric_sst_nullable(const std::string& path,
 // ---------------------------------------------------------------------------
 std::string write_table_sst(const std::string& path, const WriterCol* cols,
                             int32_t n_cols, int64_t n, int64_t row_group,
-                            int32_t codec, const PagePayload* ready) {
+                            int32_t codec, const PagePayload* ready,
+                            int32_t ba_codec) {
     if (n <= 0 || n_cols <= 0) return "write_table_sst: no rows/cols";
-    if (codec != 0 && codec != 1) return "write_table_sst: unknown codec";
+    if ((codec != 0 && codec != 1) || (ba_codec != 0 && ba_codec != 1))
+        return "write_table_sst: unknown codec";
     FILE* f = fopen(path.c_str(), "wb");
     if (!f) return "write_table_sst: cannot open " + path;
     auto fail = [&](const char* m) {
@@ -543,11 +546,30 @@ std::string write_table_sst(const std::string& path, const WriterCol* cols,
             const uint8_t* body = nullptr;
             size_t body_len = 0;
             if (wc.physical == 6) {
-                // a ready entry IS the uncompressed page image (kernel 1f);
-                // otherwise the image is built here from (bytes, offsets)
+                // a ready entry IS the uncompressed page image (kernel 1f),
+                // or under ba_codec 1 the image's Snappy stream with its
+                // size and statistics; otherwise the image is built here
+                // from (bytes, offsets)
                 const PagePayload* r6 =
                     ready && ready[g * n_cols + c].ptr
                         ? &ready[g * n_cols + c] : nullptr;
+                if (r6 && ba_codec == 1) {
+                    const BaPageStat* bs = r6->ba_stat;
+                    if (!bs || bs->min_len > BA_STAT_MAX ||
+                        bs->max_len > BA_STAT_MAX)
+                        return fail("write_table_sst: a ready BYTE_ARRAY "
+                                    "stream needs its statistics");
+                    if (r6->ulen > 0x7FFFFFFFull)
+                        return fail("write_table_sst: BYTE_ARRAY page image "
+                                    "above INT32_MAX bytes");
+                    m.has_stats = bs->has != 0;
+                    m.mn.assign((const char*)bs->min, bs->min_len);
+                    m.mx.assign((const char*)bs->max, bs->max_len);
+                    if (!pw.write(f, g, c, true, (int32_t)rows, nullptr, 0,
+                                  nullptr, r6->ulen, off, m))
+                        return fail("write failed");
+                    continue;
+                }
                 if (r6) {
                     body = r6->ptr;
                     body_len = r6->len;
@@ -618,9 +640,11 @@ std::string write_table_sst(const std::string& path, const WriterCol* cols,
                     minmax_bytes((const int64_t*)wc.data + base, rows, m.mn,
                                  m.mx);
             }
-            // BYTE_ARRAY chunks stay uncompressed under every codec
-            if (!pw.write(f, g, c, wc.physical != 6, (int32_t)rows, nullptr,
-                          0, body, body_len, off, m))
+            // BYTE_ARRAY chunks follow ba_codec (a ready stream was written
+            // above; an image built here is compressed here)
+            if (!pw.write(f, g, c,
+                          wc.physical != 6 ? codec == 1 : ba_codec == 1,
+                          (int32_t)rows, nullptr, 0, body, body_len, off, m))
                 return fail("write failed");
         }
         rgs.push_back(std::move(rg));
@@ -698,7 +722,7 @@ std::string write_metric_sst_bytes(const std::string& path,
                                    const int64_t* offsets,
                                    const uint64_t* seqs, uint64_t seq,
                                    int64_t n, int64_t row_group,
-                                   const PagePayload* ready) {
+                                   const PagePayload* ready, int32_t codec) {
     if (n <= 0) return "write_metric_sst_bytes: no rows";
     std::vector<uint64_t> zeros(n, 0), seq_col;
     if (!seqs) {
@@ -712,8 +736,7 @@ std::string write_metric_sst_bytes(const std::string& path,
         {"__seq__", 2, 14, seqs, nullptr},
         {"__reserved__", 2, 14, zeros.data(), nullptr},
     };
-    // pages stay uncompressed: staging reads no Snappy byte pages
-    return write_table_sst(path, cols, 5, n, row_group, 0, ready);
+    return write_table_sst(path, cols, 5, n, row_group, codec, ready, codec);
 }
 
 }  // namespace hx

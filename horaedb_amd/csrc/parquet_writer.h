@@ -10,6 +10,8 @@
 #include <cstdint>
 #include <string>
 
+#include "ba_pages.h"
+
 namespace hx {
 
 // Codec of the 8-byte columns' pages: 0 = UNCOMPRESSED (the default; the file
@@ -20,10 +22,15 @@ namespace hx {
 // streams made elsewhere (kernel 1e): entry [row group * n_cols + column],
 // ptr null = absent, the writer compresses that page itself. A ready stream
 // must be the twin's bytes for the page, so the file does not depend on who
-// compressed it. BYTE_ARRAY chunks stay uncompressed under every codec; a
-// ready entry for one IS its uncompressed page image (u32 length + bytes per
-// row, kernel 1f or hx::ba_build_pages_host), taken whatever the codec, and
-// its statistics are always computed by the writer from the image.
+// compressed it. BYTE_ARRAY chunks have a codec of their own (ba_codec of
+// write_table_sst, codec of write_metric_sst_bytes; 0 by default, so the index
+// tables stay uncompressed under every `codec`). Under ba_codec 0 a ready
+// entry for one IS its uncompressed page image (u32 length + bytes per row,
+// kernel 1f or hx::ba_build_pages_host) and its statistics are computed by
+// the writer from the image. Under ba_codec 1 a ready entry is the page's
+// Snappy STREAM (kernel 1e over the image, or the twin), with ulen = the
+// image's size and ba_stat = the chunk's statistics (kernel 1g or
+// hx::ba_page_minmax_host): no value byte reaches the writer.
 // A ready entry may bring the chunk's statistics too (k_page_minmax, the raw
 // 8 bytes of min and max as minmax over the column would give them); a
 // column whose every page comes ready WITH statistics may be passed as a
@@ -35,6 +42,9 @@ struct PagePayload {
                          // 1: min_bits / max_bits; 2: the chunk has none
     uint64_t min_bits;
     uint64_t max_bits;
+    // BYTE_ARRAY stream entries (ba_codec 1) only
+    uint32_t ulen = 0;                     // uncompressed page size
+    const BaPageStat* ba_stat = nullptr;   // the chunk's statistics
 };
 
 // columns are caller-provided arrays of n rows; seq is constant per file
@@ -89,7 +99,8 @@ struct WriterCol {
 std::string write_table_sst(const std::string& path, const WriterCol* cols,
                             int32_t n_cols, int64_t n, int64_t row_group,
                             int32_t codec = 0,
-                            const PagePayload* ready = nullptr);
+                            const PagePayload* ready = nullptr,
+                            int32_t ba_codec = 0);
 
 // per-row variable-length seq variant of the metric writer (general
 // compaction outputs, executor.rs:155-222 keep_builtin path)
@@ -109,15 +120,21 @@ std::string write_metric_sst_seqs(const std::string& path,
 // offsets[n + 1]) or, per row group, as a ready entry [row group * 5 + 2]
 // holding the UNCOMPRESSED page image (u32 length + bytes per row; kernel 1f
 // or hx::ba_build_pages_host); with every page ready, bytes and offsets may
-// be null. Pages are never compressed. Statistics are computed by walking the
-// page image (lexicographic min/max, omitted above 64 B), so the file is a
-// pure function of the rows whichever route built the pages.
+// be null. codec 0 (the default) writes every page uncompressed, the file it
+// always wrote; codec 1 writes all five columns' pages as Snappy streams
+// (hx::snappy_compress_host of the page bytes, the stored form for an
+// incompressible page), and a ready entry for the value column is then the
+// stream with ulen and ba_stat (PagePayload). Statistics are the
+// lexicographic min/max of the page's values, omitted above 64 B, so the file
+// is a pure function of the rows and the codec whichever route built the
+// pages.
 std::string write_metric_sst_bytes(const std::string& path,
                                    const uint64_t* series, const int64_t* ts,
                                    const uint8_t* bytes,
                                    const int64_t* offsets,
                                    const uint64_t* seqs, uint64_t seq,
                                    int64_t n, int64_t row_group,
-                                   const PagePayload* ready = nullptr);
+                                   const PagePayload* ready = nullptr,
+                                   int32_t codec = 0);
 
 }  // namespace hx

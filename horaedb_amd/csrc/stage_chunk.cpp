@@ -208,9 +208,10 @@ StageStatus stage_dictionary(const uint8_t* buf, const ChunkRef& cr,
 // Binary value column (BytesMergeOperator stores, operator.rs:47-111): the
 // PLAIN BYTE_ARRAY payload stays in the blob; per-row handles (off << 20 |
 // len) are walked by k_ba_offsets into the SST's handle array at decode time.
-// Snappy value pages would decode into the dec blob, which the handle packing
-// cannot address — the caller rejects them loudly (uncompressed and Zstd,
-// which decompresses in place, OK).
+// A handle is relative to the blob, so the body must be in the blob's own
+// offset space: uncompressed, Zstd (decompressed in place) and stored Snappy
+// pages sit in their slot, any other Snappy page is decoded into the blob's
+// tail (stage_chunk.h), never into dec.
 void stage_bytes_value(const ChunkRef& cr, const ChunkRole& role,
                        const Body& body, StagedPages& pages, ChunkResult& res) {
     BaPageDesc bp{};
@@ -279,7 +280,7 @@ StageStatus read_chunk(int fd, const std::string& path, const ChunkRef& cr,
 StageStatus stage_chunk(const uint8_t* buf, const ChunkRef& cr,
                         const ChunkRole& role, const ChunkSlot& slot,
                         std::atomic<size_t>& dec, StagedPages& pages,
-                        ChunkResult& res) {
+                        ChunkResult& res, std::atomic<size_t>* tail) {
     res = ChunkResult{};
     // layout contract: exactly one v1/v2 data page per chunk, plus an
     // optional dictionary page (RLE_DICTIONARY chunks)
@@ -373,10 +374,11 @@ StageStatus stage_chunk(const uint8_t* buf, const ChunkRef& cr,
     // payload goes into the slot verbatim, shifted by pad so the literal body
     // sits on a 64-byte boundary, and the column offset points at the body:
     // the scan kernels read it in place like an uncompressed PLAIN page (no
-    // SnappyPageDesc, no dec space). PLAIN 8-byte columns only;
-    // dictionary/DELTA pages and byte-value stores keep the decoder path.
+    // SnappyPageDesc, no dec space). PLAIN pages only, the BYTE_ARRAY value
+    // page of a Binary store included; dictionary/DELTA pages keep the
+    // decoder path.
     uint32_t body_off = 0;
-    if (snappy_page && dp.encoding == ENC_PLAIN && !value_bytes &&
+    if (snappy_page && dp.encoding == ENC_PLAIN &&
         hx_snappy_stored_literal(src, payload, (uint32_t)ulen, &body_off)) {
         // an OPTIONAL v1 page's literal opens with the level block (lvl <=
         // ulen, checked against the page size): the PLAIN body behind it is
@@ -394,6 +396,25 @@ StageStatus stage_chunk(const uint8_t* buf, const ChunkRef& cr,
             return bad(HX_ERR_FORMAT, kTooLarge);
         if (snappy_page && ulen == 0) {
             body.raw = 0;   // v2 page of nulls only: nothing to decode
+        } else if (snappy_page && value_bytes) {
+            // decoded into the blob's tail, so the handles k_ba_offsets
+            // writes stay relative to the blob
+            if (dp.encoding != ENC_PLAIN || !tail)
+                return bad(HX_ERR_UNSUPPORTED,
+                           "byte value columns support PLAIN pages only "
+                           "(uncompressed, Snappy, Zstd)");
+            // the chunk's declared size bounds what a page may claim, before
+            // anything is reserved
+            if (cr.uncomp_size < 0 || uint64_t(ulen) > uint64_t(cr.uncomp_size))
+                return bad(HX_ERR_FORMAT, kTooLarge);
+            SnappyPageDesc sp{};
+            sp.src_off = slot.off;
+            sp.comp_len = (uint32_t)payload;
+            sp.uncomp_len = (uint32_t)ulen;
+            sp.dst_off = tail->fetch_add(align64(ulen));
+            pages.snappy_ba.push_back(sp);
+            body.off = sp.dst_off + body.lvl;
+            body.raw = ulen - body.lvl;
         } else if (snappy_page) {
             SnappyPageDesc sp{};
             sp.src_off = slot.off;
@@ -410,10 +431,10 @@ StageStatus stage_chunk(const uint8_t* buf, const ChunkRef& cr,
     res.raw_size = body.raw;
 
     if (value_bytes) {
-        if (dp.encoding != ENC_PLAIN || snappy_page)
+        if (dp.encoding != ENC_PLAIN)
             return bad(HX_ERR_UNSUPPORTED,
-                       "byte value columns support PLAIN uncompressed/Zstd "
-                       "pages only");
+                       "byte value columns support PLAIN pages only "
+                       "(uncompressed, Snappy, Zstd)");
         stage_bytes_value(cr, role, body, pages, res);
         return {};
     }

@@ -80,6 +80,9 @@ struct StagedPages {
     std::vector<DeltaPageDesc> delta;
     std::vector<RleDictPageDesc> rledict;
     std::vector<BaPageDesc> ba;
+    // Snappy pages of a Binary value column: decoded into the blob's tail
+    // (dst_off counts from the blob's base, no OFF_DEC), DESIGN §3
+    std::vector<SnappyPageDesc> snappy_ba;
     uint64_t pages_in_place = 0;  // stored Snappy pages read from the blob
     uint64_t bytes_in_place = 0;
 };
@@ -110,10 +113,16 @@ StageStatus read_chunk(int fd, const std::string& path, const ChunkRef& cr,
 // space (dec bumps by align64 of what each descriptor will write) and append
 // the descriptors. Every write into the slot is bounded by slot.cap, which
 // the caller sets to chunk_reserve(cr); a page that needs more is refused.
+// tail: the cursor of the blob's decoded tail, an offset from the blob's base
+// that starts at the 64-aligned end of the slots. A Snappy page of a Binary
+// value column that is no stored literal reserves align64(uncomp_len) there
+// and is decoded to that place, so its handles stay relative to the blob;
+// without a cursor such a page is refused.
 StageStatus stage_chunk(const uint8_t* buf, const ChunkRef& cr,
                         const ChunkRole& role, const ChunkSlot& slot,
                         std::atomic<size_t>& dec, StagedPages& pages,
-                        ChunkResult& res);
+                        ChunkResult& res,
+                        std::atomic<size_t>* tail = nullptr);
 
 // Fill the RgDesc column offsets from the chunk results (results holds, rg by
 // rg in rgs order, one entry per staged column: 4 for SSTs with dense_seq,

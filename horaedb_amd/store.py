@@ -147,6 +147,13 @@ def _load():
         C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int64), C.c_void_p,
         C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.c_uint64, C.c_int64,
         C.c_int64]
+    lib.hx_write_sst_bytes_codec.argtypes = \
+        lib.hx_write_sst_bytes.argtypes + [C.c_int32]
+    lib.hx_set_bytes_write_codec.argtypes = [C.c_void_p, C.c_int32]
+    for f in (lib.hx_debug_ba_page_minmax, lib.hx_debug_ba_page_minmax_host):
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_uint64),
+                      C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32,
+                      C.c_void_p]
     for f in (lib.hx_debug_ba_pages, lib.hx_debug_ba_pages_host):
         f.argtypes = [
             C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_uint32,
@@ -472,6 +479,12 @@ class Store:
         set_nullable_values."""
         _check(_lib.hx_set_write_codec(self._h, int(codec)))
 
+    def set_bytes_write_codec(self, codec):
+        """Writer setting of a Binary store (hx_set_bytes_write_codec):
+        CODEC_NONE (default) or CODEC_SNAPPY, the page codec of every SST
+        write_bytes, compact and compact_files write from now on."""
+        _check(_lib.hx_set_bytes_write_codec(self._h, int(codec)))
+
     def write(self, series, ts, value, enable_check=True, valid=None):
         """ColumnarStorage::write (storage.rs:76-89): stable PK sort + new
         SST + catalog add. Returns the new file's sequence. valid: bool
@@ -642,21 +655,25 @@ def _bytes_col(values, n):
 
 
 def write_sst_native_bytes(path, series, ts, values, seq, seqs=None,
-                           row_group=8192):
+                           row_group=8192, codec=0):
     """GPU-free writer of one Binary-value SST (hx_write_sst_bytes), rows in
     the order given. seqs: per-row __seq__ values, or None for the constant
-    seq."""
+    seq. codec: CODEC_NONE (default, the old entry) or CODEC_SNAPPY
+    (hx_write_sst_bytes_codec)."""
     series = np.ascontiguousarray(series, dtype=np.uint64)
     ts = np.ascontiguousarray(ts, dtype=np.int64)
     n = len(series)
     blob, offs = _bytes_col(values, n)
     sq = None if seqs is None else np.ascontiguousarray(seqs, dtype=np.uint64)
-    _check(_lib.hx_write_sst_bytes(
-        path.encode(), series.ctypes.data_as(C.POINTER(C.c_uint64)),
-        ts.ctypes.data_as(C.POINTER(C.c_int64)), blob.ctypes.data,
-        offs.ctypes.data_as(C.POINTER(C.c_int64)),
-        None if sq is None else sq.ctypes.data_as(C.POINTER(C.c_uint64)),
-        int(seq), n, row_group))
+    args = (path.encode(), series.ctypes.data_as(C.POINTER(C.c_uint64)),
+            ts.ctypes.data_as(C.POINTER(C.c_int64)), blob.ctypes.data,
+            offs.ctypes.data_as(C.POINTER(C.c_int64)),
+            None if sq is None else sq.ctypes.data_as(C.POINTER(C.c_uint64)),
+            int(seq), n, row_group)
+    if codec:
+        _check(_lib.hx_write_sst_bytes_codec(*args, int(codec)))
+    else:
+        _check(_lib.hx_write_sst_bytes(*args))
 
 
 def _ba_pages_call(fn, src, handles, group_start, n_out, row_group, build):
@@ -708,6 +725,62 @@ def ba_pages_device(src, handles, group_start=None, n_out=None,
     Arguments and result as ba_pages_host."""
     return _ba_pages_call(_lib.hx_debug_ba_pages, src, handles, group_start,
                           n_out, row_group, build)
+
+
+BA_ROW_SKIP = 0x80000000
+
+
+def _ba_page_minmax_call(fn, values, row_group, skip):
+    skip = set(skip)
+    n = len(values)
+    vals = [b"" if i in skip else bytes(v) for i, v in enumerate(values)]
+    row_len = np.array([BA_ROW_SKIP if i in skip else len(v)
+                        for i, v in enumerate(vals)], dtype=np.uint32)
+    n_pages = (n + row_group - 1) // row_group
+    page_off = np.zeros(n_pages + 1, dtype=np.uint64)
+    parts = []
+    for g in range(n_pages):
+        page = b"".join(len(v).to_bytes(4, "little") + v
+                        for v in vals[g * row_group:(g + 1) * row_group])
+        parts.append(page)
+        page_off[g + 1] = page_off[g] + np.uint64(len(page))
+    image = np.frombuffer(b"".join(parts), dtype=np.uint8)
+    out = np.full(n_pages * 140, 0xA5, dtype=np.uint8)
+    _check(fn(image.ctypes.data,
+              page_off.ctypes.data_as(C.POINTER(C.c_uint64)),
+              row_len.ctypes.data_as(C.POINTER(C.c_uint32)), n, row_group,
+              out.ctypes.data))
+    res = []
+    for g in range(n_pages):
+        rec = out[g * 140:(g + 1) * 140]
+        has, mn_len, mx_len = (int(x) for x in rec[:12].view(np.uint32))
+        mn, mx = rec[12:76].tobytes(), rec[76:140].tobytes()
+        if mn_len > 64 or mx_len > 64 or any(mn[mn_len:]) or any(mx[mx_len:]):
+            raise AssertionError("BaPageStat record out of form: %r" % (
+                (has, mn_len, mx_len, mn, mx),))
+        if not has and (mn_len or mx_len):
+            raise AssertionError("BaPageStat without statistics has lengths")
+        res.append((mn[:mn_len], mx[:mx_len]) if has else None)
+    return res
+
+
+def ba_page_minmax_host(values, row_group=8192, skip=()):
+    """The host twin of kernel 1g (test hook hx_debug_ba_page_minmax_host; no
+    GPU needed) over the PLAIN BYTE_ARRAY page images of `values` (a sequence
+    of bytes), row groups of row_group rows. skip: indices of rows the size
+    pass refused (BA_ROW_SKIP): they are empty values in the image. Returns
+    one entry per page: (min, max) as bytes, or None when the chunk carries
+    no min/max (one of them is longer than 64 bytes)."""
+    return _ba_page_minmax_call(_lib.hx_debug_ba_page_minmax_host, values,
+                                row_group, skip)
+
+
+def ba_page_minmax_device(values, row_group=8192, skip=()):
+    """Kernel 1g through the test hook hx_debug_ba_page_minmax (needs a GPU):
+    the production launch over device buffers of exactly the stated sizes.
+    Arguments and result as ba_page_minmax_host."""
+    return _ba_page_minmax_call(_lib.hx_debug_ba_page_minmax, values,
+                                row_group, skip)
 
 
 def _validity_bits(valid, n):

@@ -349,7 +349,14 @@ hx_status hx_write_sst_codec(const char* path, const uint64_t* series,
 /* ---- Binary value stores: the write side ------------------------------
  * The schema behind BytesMergeOperator / UpdateMode::Append: series_id,
  * timestamp, value (BYTE_ARRAY), __seq__, __reserved__, all REQUIRED, pages
- * PLAIN and uncompressed. THE VALUE LIMIT: a value is at most 2^20 - 1
+ * PLAIN, uncompressed by default or Snappy (hx_set_bytes_write_codec, the
+ * reference's on-disk form). Read side: value pages may be uncompressed,
+ * Snappy or Zstd, data page v1 or v2, the column REQUIRED or OPTIONAL
+ * without nulls (the reference declares every column nullable); a null in
+ * the value column, and a value chunk of more than one data page, are
+ * refused with HX_ERR_UNSUPPORTED. A Snappy value page is decoded on the
+ * device into a tail of the staged blob, so value handles keep one base.
+ * THE VALUE LIMIT: a value is at most 2^20 - 1
  * bytes, because the reader describes a value by a handle with 20 length
  * bits (k_ba_offsets refuses a longer one at read time). Every writer
  * enforces it: a longer value given to hx_write_bytes / hx_write_sst_bytes
@@ -391,6 +398,33 @@ hx_status hx_write_sst_bytes(const char* path, const uint64_t* series,
                              const int64_t* ts, const uint8_t* bytes,
                              const int64_t* offsets, const uint64_t* seqs,
                              uint64_t seq, int64_t n_rows, int64_t row_group);
+
+/* Page codec of the Binary writers, per handle; default HX_CODEC_NONE
+ * (nothing changes: the files are what they always were, byte for byte).
+ * With HX_CODEC_SNAPPY every SST that hx_write_bytes, hx_compact and
+ * hx_compact_files write on a Binary store carries Snappy pages in all five
+ * columns. A page's stream is a function of the page bytes alone (the stored
+ * form for an incompressible page), and the footer statistics of a value
+ * chunk are the lexicographic min/max of its values (omitted above 64
+ * bytes), so a file does not depend on the route that wrote it: host ingest,
+ * device ingest, either compaction, or hx_write_sst_bytes_codec. On the
+ * device routes the page images never reach the host: statistics and streams
+ * are made where the images lie.
+ * hx_set_write_codec keeps its meaning and its refusals; this is a setting
+ * of its own. An unknown codec returns HX_ERR_INVALID; HX_CODEC_SNAPPY on a
+ * store with an f64 value column returns HX_ERR_UNSUPPORTED; on an empty
+ * store it is accepted, and hx_write / hx_write_nullable then return
+ * HX_ERR_UNSUPPORTED. Every refusal comes before anything is written. */
+hx_status hx_set_bytes_write_codec(hx_handle*, int32_t codec);
+
+/* hx_write_sst_bytes with a codec; codec 0 writes the file
+ * hx_write_sst_bytes writes, byte for byte. */
+hx_status hx_write_sst_bytes_codec(const char* path, const uint64_t* series,
+                                   const int64_t* ts, const uint8_t* bytes,
+                                   const int64_t* offsets,
+                                   const uint64_t* seqs, uint64_t seq,
+                                   int64_t n_rows, int64_t row_group,
+                                   int32_t codec);
 
 /* ---- inverted index (RFC docs/rfcs/20240827-metric-engine.md:86-137) ----
  * The reference's planned index tables (its metric_engine index module is

@@ -195,10 +195,16 @@ def gen_dataset(out_dir, n_rows, n_series, n_ssts, seed=42,
 
 
 def write_bytes_sst(path, series, ts, values, seq, row_group=8192,
-                    sort=True):
+                    sort=True, compression="NONE", nullable=False,
+                    data_page_version="1.0", data_page_size=None):
     """One Binary-value SST (BytesMergeOperator stores, operator.rs:47-111):
-    (series u64 PK, ts i64 PK, value binary, builtins), PLAIN uncompressed,
-    writer-sorted by (series, ts) stable (equal PKs keep input order)."""
+    (series u64 PK, ts i64 PK, value binary, builtins), PLAIN, writer-sorted
+    by (series, ts) stable (equal PKs keep input order). compression: "NONE"
+    (default), "SNAPPY" (the reference's default, config.rs:120-133) or
+    "ZSTD". nullable: every column is declared OPTIONAL, the reference's
+    shape; a value may then be None. data_page_size: pyarrow's page-size
+    limit; the reader takes one data page per chunk, so give one above the
+    largest value page (the default splits a chunk at 1 MiB)."""
     import pyarrow as pa
     import pyarrow.parquet as pq
     series = np.asarray(series, dtype=np.uint64)
@@ -211,27 +217,30 @@ def write_bytes_sst(path, series, ts, values, seq, row_group=8192,
         values = [values[i] for i in order]
     n = len(series)
     schema = pa.schema([
-        pa.field("series_id", pa.uint64(), nullable=False),
-        pa.field("timestamp", pa.int64(), nullable=False),
-        pa.field("value", pa.binary(), nullable=False),
-        pa.field("__seq__", pa.uint64(), nullable=False),
-        pa.field("__reserved__", pa.uint64(), nullable=False),
+        pa.field("series_id", pa.uint64(), nullable=nullable),
+        pa.field("timestamp", pa.int64(), nullable=nullable),
+        pa.field("value", pa.binary(), nullable=nullable),
+        pa.field("__seq__", pa.uint64(), nullable=nullable),
+        pa.field("__reserved__", pa.uint64(), nullable=nullable),
     ])
     tbl = pa.table({
         "series_id": pa.array(series, pa.uint64()),
         "timestamp": pa.array(ts, pa.int64()),
-        "value": pa.array([v if isinstance(v, bytes) else v.encode()
-                           for v in values], pa.binary()),
+        "value": pa.array([v if v is None or isinstance(v, bytes)
+                           else v.encode() for v in values], pa.binary()),
         "__seq__": pa.array(np.full(n, seq, np.uint64), pa.uint64()),
         "__reserved__": pa.array(np.zeros(n, np.uint64), pa.uint64()),
     }, schema=schema)
     os.makedirs(os.path.dirname(path), exist_ok=True)
-    pq.write_table(tbl, path, row_group_size=row_group, compression="NONE",
-                   use_dictionary=False, data_page_version="1.0",
+    extra = {} if data_page_size is None else \
+        {"data_page_size": int(data_page_size)}
+    pq.write_table(tbl, path, row_group_size=row_group,
+                   compression=compression, use_dictionary=False,
+                   data_page_version=data_page_version,
                    column_encoding={c: "PLAIN" for c in
                                     ("series_id", "timestamp", "value",
                                      "__seq__", "__reserved__")},
-                   write_statistics=True)
+                   write_statistics=True, **extra)
     return path
 
 
