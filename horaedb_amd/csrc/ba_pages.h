@@ -2,7 +2,9 @@
 // kernels.hip): the PLAIN BYTE_ARRAY page images of a Binary
 // `value` column, built from per-row handles. No GPU header is included; the
 // stand-alone check (ba_pages_check.cpp) compiles this file with a host
-// compiler under ASan/UBSan.
+// compiler under ASan/UBSan. Further down: the rule that cuts a row group's
+// image into data pages with kernel 1h's twin (ba_multipage_check.cpp), and
+// kernel 1g's twin.
 //
 // A handle is what k_ba_offsets leaves per row: (offset << 20) | length, the
 // offset relative to a source base of src_size bytes. The 20 length bits are
@@ -135,6 +137,78 @@ inline void ba_build_pages_host(const uint8_t* src, uint64_t src_size,
             p += len;
         }
     }
+}
+
+// ---------------------------------------------------------------------------
+// Data pages of a value chunk (kernel 1h). A row group's image may
+// be cut into several data pages, by the rule arrow-cpp's column writer
+// applies (and, to our knowledge, parquet-rs: DESIGN §10): rows are taken in
+// batches of BA_CUT_BATCH counted from the row group's first row; a row adds
+// 4 + len to the open page (4 for a BA_ROW_SKIP row); after a batch, a page
+// that has reached `limit` bytes closes if rows remain; the last page closes
+// at the row group's end. So there are at most ceil(rows / 1024) pages, none
+// of them empty, and the cuts are a pure function of the rows. limit 0 means
+// one page per row group. This is the one statement of the rule: it works on
+// the per-batch byte sums, which the host computes from row_len
+// (ba_batch_sizes_host) and the device with k_ba_batch_sizes.
+// ---------------------------------------------------------------------------
+constexpr uint32_t BA_CUT_BATCH = 1024;
+constexpr uint32_t BA_PAGE_LIMIT_MAX = 1u << 30;
+
+inline uint64_t ba_batches_per_group(uint64_t R) {
+    return (R + BA_CUT_BATCH - 1) / BA_CUT_BATCH;
+}
+// batches of n_out rows in row groups of R: every row group but the last is
+// full, batch b covers rows [g * R + j * 1024, ...) with g = b / per_group,
+// j = b % per_group, clipped to its row group and to n_out
+inline uint64_t ba_n_batches(uint64_t n_out, uint64_t R) {
+    const uint64_t n_rg = ba_n_pages(n_out, R);
+    if (n_rg == 0) return 0;
+    const uint64_t last = n_out - (n_rg - 1) * R;
+    return (n_rg - 1) * ba_batches_per_group(R) +
+           (last + BA_CUT_BATCH - 1) / BA_CUT_BATCH;
+}
+
+// Host twin of k_ba_batch_sizes: batch_sum[ba_n_batches(n_out, R)].
+inline void ba_batch_sizes_host(const uint32_t* row_len, uint64_t n_out,
+                                uint64_t R, uint64_t* batch_sum) {
+    const uint64_t per = ba_batches_per_group(R);
+    const uint64_t n_b = ba_n_batches(n_out, R);
+    for (uint64_t b = 0; b < n_b; b++) {
+        const uint64_t g = b / per, j = b % per;
+        const uint64_t r0 = g * R + j * BA_CUT_BATCH;
+        uint64_t r1 = r0 + BA_CUT_BATCH;
+        if (r1 > (g + 1) * R) r1 = (g + 1) * R;
+        if (r1 > n_out) r1 = n_out;
+        uint64_t sum = 0;
+        for (uint64_t i = r0; i < r1; i++)
+            sum += 4ull + ((row_len[i] & BA_ROW_SKIP) ? 0u : row_len[i]);
+        batch_sum[b] = sum;
+    }
+}
+
+// THE RULE, for one row group of `rows` rows whose batches' byte sums are
+// batch_sum[0, ceil(rows / 1024)). Writes the pages' row counts and byte
+// sizes (room for ceil(rows / 1024) entries each, at least one) and returns
+// the number of pages: 0 only for rows == 0.
+inline uint32_t ba_cut_pages(const uint64_t* batch_sum, uint64_t rows,
+                             uint32_t limit, uint32_t* page_rows,
+                             uint64_t* page_bytes) {
+    uint32_t k = 0;
+    uint64_t open_rows = 0, open_bytes = 0;
+    for (uint64_t r0 = 0, j = 0; r0 < rows; r0 += BA_CUT_BATCH, j++) {
+        const uint64_t n = rows - r0 < BA_CUT_BATCH ? rows - r0 : BA_CUT_BATCH;
+        open_rows += n;
+        open_bytes += batch_sum[j];
+        const bool more = r0 + n < rows;
+        if (!more || (limit != 0 && open_bytes >= limit)) {
+            page_rows[k] = uint32_t(open_rows);
+            page_bytes[k] = open_bytes;
+            k++;
+            open_rows = open_bytes = 0;
+        }
+    }
+    return k;
 }
 
 // ---------------------------------------------------------------------------

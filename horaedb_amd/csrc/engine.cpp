@@ -103,6 +103,8 @@ struct hx_handle {
                                          // (hx_set_write_codec)
     int32_t bytes_write_codec = 0;       // the same for the Binary writers
                                          // (hx_set_bytes_write_codec)
+    uint32_t bytes_page_limit = 0;       // data-page limit of their value
+                                         // chunks (hx_set_bytes_page_limit)
     std::vector<CatSst> ssts;            // ascending seq
     std::vector<hx_sst_desc> find_out;   // scratch for hx_find_ssts
 };
@@ -314,6 +316,19 @@ extern "C" hx_status hx_set_bytes_write_codec(hx_handle* h, int32_t codec) {
         return fail(HX_ERR_UNSUPPORTED,
                     "a bytes write codec needs a Binary value column");
     h->bytes_write_codec = codec;
+    return HX_OK;
+}
+
+// Data-page limit of the Binary writers' value chunks (hx::ba_cut_pages).
+// 0 launches and writes exactly what it always did: one page per chunk.
+extern "C" hx_status hx_set_bytes_page_limit(hx_handle* h, uint32_t bytes) {
+    if (!h || bytes > hx::BA_PAGE_LIMIT_MAX)
+        return fail(HX_ERR_INVALID,
+                    "bytes page limit: 0 (one page per chunk) or 1 .. 2^30");
+    if (bytes != 0 && !h->bytes_value && !h->ssts.empty())
+        return fail(HX_ERR_UNSUPPORTED,
+                    "a bytes page limit needs a Binary value column");
+    h->bytes_page_limit = bytes;
     return HX_OK;
 }
 
@@ -3269,15 +3284,16 @@ namespace {
 const char kBaLimit[] =
     "2^20 - 1 bytes (a value handle has 20 length bits)";
 
-// The one refusal of a value page above Parquet's i32 page sizes (and
-// BaPageDesc::src_len): page_off has n_pages + 1 entries.
+// The one refusal of a row group's value image above Parquet's i32 page sizes
+// (and BaPageDesc::src_len; with or without a page limit, read_chunk needs
+// it too): page_off has n_pages + 1 entries.
 hx_status check_page_sizes(const uint64_t* page_off, uint64_t n_pages) {
     for (uint64_t g = 0; g < n_pages; g++)
         if (page_off[g + 1] - page_off[g] > hx::BA_MAX_PAGE_BYTES)
             return fail(HX_ERR_UNSUPPORTED,
                         "row group " + std::to_string(g) + ": the value "
-                        "page would exceed INT32_MAX bytes (multi-page "
-                        "chunks are not written)");
+                        "image would exceed INT32_MAX bytes (a page limit "
+                        "cuts the image, it does not lift this bound)");
     return HX_OK;
 }
 
@@ -3311,29 +3327,43 @@ struct BaPageBuilder {
     DevBufs dev;
     uint32_t* d_row_len = nullptr;
     unsigned long long* d_words = nullptr;   // page_off[n_pages + 1],
-                                             // counts[2], page_size[n_pages]
-    uint32_t n_pages = 0;
-    std::vector<uint64_t> page_off;          // n_pages + 1, counts behind
+                                             // counts[2], batch_sum[n_batches],
+                                             // page_size[n_pages]
+    uint32_t n_pages = 0;                    // row groups (one image each)
+    uint32_t n_batches = 0;                  // 0 without a page limit
+    std::vector<uint64_t> page_off;          // n_pages + 1, counts and the
+                                             // batch sums behind
     uint64_t n_errors = 0, n_over_cap = 0;
+
+    const uint64_t* batch_sum() const {
+        return n_batches ? page_off.data() + n_pages + 3 : nullptr;
+    }
 
     uint64_t total() const { return page_off[n_pages]; }
 
-    // launches, one small D2H, no verdict yet
+    // launches, one small D2H, no verdict yet. With a page limit kernel 1h
+    // adds the 1024-row batch sums, which ride home in the same copy.
     hx_status run(hipStream_t s, uint64_t src_size, const uint64_t* d_handles,
                   const uint32_t* d_group_start, uint32_t n_src,
-                  uint32_t n_out, uint32_t row_group) {
+                  uint32_t n_out, uint32_t row_group,
+                  uint32_t page_limit = 0) {
         n_pages = (uint32_t)hx::ba_n_pages(n_out, row_group);
+        n_batches =
+            page_limit ? (uint32_t)hx::ba_n_batches(n_out, row_group) : 0;
+        const size_t head = size_t(n_pages) + 3 + n_batches;
         HIP_TRY(dev.alloc((void**)&d_row_len, size_t(n_out) * 4));
-        HIP_TRY(dev.alloc((void**)&d_words, (2 * size_t(n_pages) + 3) * 8));
+        HIP_TRY(dev.alloc((void**)&d_words, (head + size_t(n_pages)) * 8));
         unsigned long long* d_counts = d_words + n_pages + 1;
         HIP_TRY(hipMemsetAsync(d_counts, 0, 16, s));
         HIP_TRY(hx::launch_ba_page_sizes(s, src_size, d_handles,
                                          d_group_start, n_src, n_out,
-                                         row_group, d_row_len, d_counts + 2,
+                                         row_group, d_row_len, d_words + head,
                                          d_words, d_counts));
-        page_off.resize(size_t(n_pages) + 3);
-        HIP_TRY(hipMemcpyAsync(page_off.data(), d_words,
-                               (size_t(n_pages) + 3) * 8,
+        if (n_batches)
+            HIP_TRY(hx::launch_ba_batch_sizes(s, d_row_len, n_out, row_group,
+                                              d_counts + 2));
+        page_off.resize(head);
+        HIP_TRY(hipMemcpyAsync(page_off.data(), d_words, head * 8,
                                hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         n_errors = page_off[n_pages + 1];
@@ -3354,14 +3384,76 @@ struct BaPageBuilder {
     }
 };
 
+// The data pages of a value column: row group g holds pages [first[g],
+// first[g + 1]), each with its rows and uncompressed bytes. Without a limit
+// every row group is one page; with one, hx::ba_cut_pages over the batch sums
+// (kernel 1h's or hx::ba_batch_sizes_host's) says where the pages end.
+struct BaCuts {
+    std::vector<uint32_t> first, rows, ulen;
+    uint32_t n() const { return (uint32_t)rows.size(); }
+};
+
+BaCuts ba_cuts(const uint64_t* batch_sum, const uint64_t* page_off,
+               uint32_t n_rg, uint64_t n_out, uint32_t limit) {
+    BaCuts c;
+    c.first.assign(1, 0);
+    const uint64_t per = hx::ba_batches_per_group(kRowGroup);
+    std::vector<uint32_t> pr(per ? per : 1);
+    std::vector<uint64_t> pb(per ? per : 1);
+    for (uint32_t g = 0; g < n_rg; g++) {
+        const uint64_t rows =
+            std::min<uint64_t>(kRowGroup, n_out - uint64_t(g) * kRowGroup);
+        if (limit && batch_sum) {
+            const uint32_t k = hx::ba_cut_pages(batch_sum + g * per, rows,
+                                                limit, pr.data(), pb.data());
+            for (uint32_t i = 0; i < k; i++) {
+                c.rows.push_back(pr[i]);
+                c.ulen.push_back(uint32_t(pb[i]));
+            }
+        } else {
+            c.rows.push_back(uint32_t(rows));
+            c.ulen.push_back(uint32_t(page_off[g + 1] - page_off[g]));
+        }
+        c.first.push_back(c.n());
+    }
+    return c;
+}
+
+// The pages of every row group must add up to its image, byte for byte,
+// before a device pass slices the image by them.
+hx_status check_cuts(const BaCuts& c, const uint64_t* page_off,
+                     uint32_t n_rg) {
+    for (uint32_t g = 0; g < n_rg; g++) {
+        uint64_t sum = 0;
+        for (uint32_t p = c.first[g]; p < c.first[g + 1]; p++)
+            sum += c.ulen[p];
+        if (sum != page_off[g + 1] - page_off[g])
+            return fail(HX_ERR_HIP, "byte pages: the batch sums do not add "
+                                    "up to the row group's image");
+    }
+    return HX_OK;
+}
+
+// a ready entry's cuts (none for a row group of one page: the entry it
+// always was)
+void ba_ready_split(hx::PagePayload& r, const BaCuts& cuts, uint32_t g) {
+    const uint32_t k = cuts.first[g + 1] - cuts.first[g];
+    if (k <= 1) return;
+    r.n_split = k;
+    r.split_rows = cuts.rows.data() + cuts.first[g];
+    r.split_ulen = cuts.ulen.data() + cuts.first[g];
+}
+
 // ready table of the 5-column metric layout: the value column's page images
 std::vector<hx::PagePayload> ba_ready(const uint64_t* page_off,
                                       uint32_t n_pages,
-                                      const uint8_t* image) {
+                                      const uint8_t* image,
+                                      const BaCuts& cuts) {
     std::vector<hx::PagePayload> r(size_t(n_pages) * 5, hx::PagePayload{});
     for (uint32_t g = 0; g < n_pages; g++) {
         r[size_t(g) * 5 + 2].ptr = image + page_off[g];
         r[size_t(g) * 5 + 2].len = uint32_t(page_off[g + 1] - page_off[g]);
+        ba_ready_split(r[size_t(g) * 5 + 2], cuts, g);
     }
     return r;
 }
@@ -3371,8 +3463,8 @@ std::vector<hx::PagePayload> ba_ready(const uint64_t* page_off,
 // ba_stat), whoever made them.
 struct BaStreams {
     std::vector<uint8_t> bytes;          // the streams, back to back
-    std::vector<uint32_t> lens;          // per page
-    std::vector<hx::BaPageStat> stats;   // per page
+    std::vector<uint32_t> lens;          // per data page (BaCuts order)
+    std::vector<hx::BaPageStat> stats;   // per row group
     size_t d2h_bytes = 0;                // device route: what came back
     float stats_ms = 0, compress_ms = 0; // device route under HX_DEBUG
 };
@@ -3380,44 +3472,53 @@ struct BaStreams {
 // the host route: hx::ba_page_minmax_host and hx::snappy_compress_host
 void ba_streams_host(const uint8_t* image, const uint64_t* page_off,
                      uint32_t n_pages, const uint32_t* row_len,
-                     uint64_t n_out, BaStreams& out) {
+                     uint64_t n_out, const BaCuts& cuts, BaStreams& out) {
     out.stats.resize(n_pages);
-    out.lens.resize(n_pages);
+    out.lens.resize(cuts.n());
     hx::ba_page_minmax_host(image, page_off, row_len, n_out, kRowGroup,
                             out.stats.data());
     out.bytes.clear();
     for (uint32_t g = 0; g < n_pages; g++) {
-        const size_t n = size_t(page_off[g + 1] - page_off[g]);
-        const size_t at = out.bytes.size();
-        out.bytes.resize(at + size_t(hx::snappy_max_compressed(n)));
-        const size_t got = hx::snappy_compress_host(
-            image + page_off[g], n, out.bytes.data() + at,
-            out.bytes.size() - at);
-        out.lens[g] = uint32_t(got);
-        out.bytes.resize(at + got);
+        size_t src = size_t(page_off[g]);
+        for (uint32_t p = cuts.first[g]; p < cuts.first[g + 1]; p++) {
+            const size_t n = cuts.ulen[p];
+            const size_t at = out.bytes.size();
+            out.bytes.resize(at + size_t(hx::snappy_max_compressed(n)));
+            const size_t got = hx::snappy_compress_host(
+                image + src, n, out.bytes.data() + at, out.bytes.size() - at);
+            out.lens[p] = uint32_t(got);
+            out.bytes.resize(at + got);
+            src += n;
+        }
     }
 }
 
 // the value column's entries of a ready table (n_pages * 5 entries)
 void ba_ready_streams(std::vector<hx::PagePayload>& ready,
                       const uint64_t* page_off, uint32_t n_pages,
-                      const BaStreams& st) {
+                      const BaCuts& cuts, const BaStreams& st) {
     ready.resize(size_t(n_pages) * 5, hx::PagePayload{});
     size_t at = 0;
     for (uint32_t g = 0; g < n_pages; g++) {
         hx::PagePayload& r = ready[size_t(g) * 5 + 2];
         r = hx::PagePayload{};
         r.ptr = st.bytes.data() + at;
-        r.len = st.lens[g];
+        uint32_t len = 0;
+        for (uint32_t p = cuts.first[g]; p < cuts.first[g + 1]; p++)
+            len += st.lens[p];
+        r.len = len;
         r.ulen = uint32_t(page_off[g + 1] - page_off[g]);
         r.ba_stat = &st.stats[g];
-        at += st.lens[g];
+        ba_ready_split(r, cuts, g);
+        if (r.n_split) r.split_len = st.lens.data() + cuts.first[g];
+        at += len;
     }
 }
 
-// The device route: kernel 1g over the image kernel 1f left in HBM, kernel 1e
-// with one SnappyCompDesc per page image (slots at Snappy's bound; n and
-// dst_cap are u32, which a page of at most INT32_MAX bytes fits), the
+// The device route: kernel 1g over the image kernel 1f left in HBM (per row
+// group), kernel 1e with one SnappyCompDesc per DATA PAGE (cuts: consecutive
+// slices of each row group's image; slots at Snappy's bound; n and dst_cap
+// are u32, which a page of at most INT32_MAX bytes fits), the
 // scan-and-pack pass, then lengths + statistics and ONE contiguous copy of
 // the streams. d_page_off / d_row_len as the size pass left them; page_off
 // its host copy (every page already checked against BA_MAX_PAGE_BYTES).
@@ -3426,26 +3527,32 @@ hipError_t compress_ba_pages_device(hipStream_t s, const uint8_t* d_image,
                                     uint32_t n_pages,
                                     const unsigned long long* d_page_off,
                                     const uint32_t* d_row_len, uint32_t n_out,
-                                    bool timed, BaStreams& out) {
-    std::vector<hx::SnappyCompDesc> descs(n_pages);
+                                    const BaCuts& cuts, bool timed,
+                                    BaStreams& out) {
+    const uint32_t n_descs = cuts.n();
+    std::vector<hx::SnappyCompDesc> descs(n_descs);
     size_t slot_bytes = 0;
     for (uint32_t g = 0; g < n_pages; g++) {
-        hx::SnappyCompDesc& d = descs[g];
-        d.src_off = page_off[g];
-        d.n = uint32_t(page_off[g + 1] - page_off[g]);
-        d.dst_cap = uint32_t(hx::snappy_max_compressed(d.n));
-        d.dst_off = slot_bytes;
-        slot_bytes = align64(slot_bytes + d.dst_cap);
+        uint64_t src = page_off[g];
+        for (uint32_t p = cuts.first[g]; p < cuts.first[g + 1]; p++) {
+            hx::SnappyCompDesc& d = descs[p];
+            d.src_off = src;
+            d.n = cuts.ulen[p];
+            d.dst_cap = uint32_t(hx::snappy_max_compressed(d.n));
+            d.dst_off = slot_bytes;
+            slot_bytes = align64(slot_bytes + d.dst_cap);
+            src += d.n;
+        }
     }
     out.bytes.clear();
-    out.lens.assign(n_pages, 0);
+    out.lens.assign(n_descs, 0);
     out.stats.assign(n_pages, hx::BaPageStat{});
     out.d2h_bytes = 0;
     if (n_pages == 0) return hipSuccess;
-    const size_t desc_bytes = align64(size_t(n_pages) * sizeof(descs[0]));
-    const size_t off_bytes = align64(size_t(n_pages) * 8);
+    const size_t desc_bytes = align64(size_t(n_descs) * sizeof(descs[0]));
+    const size_t off_bytes = align64(size_t(n_descs) * 8);
     // read back first, in one copy: lengths, error count, statistics
-    const size_t len_bytes = (size_t(n_pages) * 4 + 7) & ~size_t(7);
+    const size_t len_bytes = (size_t(n_descs) * 4 + 7) & ~size_t(7);
     const size_t stat_bytes = size_t(n_pages) * sizeof(hx::BaPageStat);
     const size_t back_bytes = len_bytes + 8 + stat_bytes;
     uint8_t* dev = nullptr;
@@ -3474,16 +3581,16 @@ hipError_t compress_ba_pages_device(hipStream_t s, const uint8_t* d_image,
     if (timed)
         for (auto& v : ev) BS_TRY(hipEventCreate(&v));
     BS_TRY(hipMemcpyAsync(d_descs, descs.data(),
-                          size_t(n_pages) * sizeof(descs[0]),
+                          size_t(n_descs) * sizeof(descs[0]),
                           hipMemcpyHostToDevice, s));
     BS_TRY(hipMemsetAsync(d_err, 0, 8, s));
     if (timed) BS_TRY(hipEventRecord(ev[0], s));
     BS_TRY(hx::launch_ba_page_minmax(s, d_image, d_page_off, d_row_len, n_out,
                                      (uint32_t)kRowGroup, d_stats));
     if (timed) BS_TRY(hipEventRecord(ev[1], s));
-    BS_TRY(hx::launch_snappy_compress(s, d_image, d_slots, d_descs, n_pages,
+    BS_TRY(hx::launch_snappy_compress(s, d_image, d_slots, d_descs, n_descs,
                                       d_lens, d_err));
-    BS_TRY(hx::launch_snappy_pack(s, d_slots, d_descs, n_pages, d_lens,
+    BS_TRY(hx::launch_snappy_pack(s, d_slots, d_descs, n_descs, d_lens,
                                   d_offs, d_packed));
     if (timed) BS_TRY(hipEventRecord(ev[2], s));
     std::vector<uint64_t> back((back_bytes + 7) / 8);
@@ -3491,11 +3598,11 @@ hipError_t compress_ba_pages_device(hipStream_t s, const uint8_t* d_image,
                           hipMemcpyDeviceToHost, s));
     BS_TRY(hipStreamSynchronize(s));
     if (back[len_bytes / 8] != 0) return hipErrorUnknown;
-    std::memcpy(out.lens.data(), back.data(), size_t(n_pages) * 4);
+    std::memcpy(out.lens.data(), back.data(), size_t(n_descs) * 4);
     std::memcpy(out.stats.data(), (const uint8_t*)back.data() + len_bytes + 8,
                 stat_bytes);
     size_t total = 0;
-    for (uint32_t g = 0; g < n_pages; g++) total += out.lens[g];
+    for (uint32_t p = 0; p < n_descs; p++) total += out.lens[p];
     out.bytes.resize(total);
     BS_TRY(hipMemcpyAsync(out.bytes.data(), d_packed, total,
                           hipMemcpyDeviceToHost, s));
@@ -3543,8 +3650,20 @@ extern "C" hx_status hx_write_sst_bytes_codec(
     const char* path, const uint64_t* series, const int64_t* ts,
     const uint8_t* bytes, const int64_t* offsets, const uint64_t* seqs,
     uint64_t seq, int64_t n_rows, int64_t row_group, int32_t codec) {
+    return hx_write_sst_bytes_paged(path, series, ts, bytes, offsets, seqs,
+                                    seq, n_rows, row_group, codec, 0);
+}
+
+extern "C" hx_status hx_write_sst_bytes_paged(
+    const char* path, const uint64_t* series, const int64_t* ts,
+    const uint8_t* bytes, const int64_t* offsets, const uint64_t* seqs,
+    uint64_t seq, int64_t n_rows, int64_t row_group, int32_t codec,
+    uint32_t page_limit) {
     if (!path || !series || !ts || !offsets || n_rows <= 0 || row_group <= 0)
         return fail(HX_ERR_INVALID, "bad argument");
+    if (page_limit > hx::BA_PAGE_LIMIT_MAX)
+        return fail(HX_ERR_INVALID,
+                    "bytes page limit: 0 (one page per chunk) or 1 .. 2^30");
     if (codec != HX_CODEC_NONE && codec != HX_CODEC_SNAPPY)
         return fail(HX_ERR_INVALID, "write codec: 0 none / 1 snappy");
     hx_status st = check_value_offsets(offsets, n_rows);
@@ -3561,11 +3680,13 @@ extern "C" hx_status hx_write_sst_bytes_codec(
     st = check_page_sizes(page_off.data(), page_off.size() - 1);
     if (st != HX_OK) return st;
     // the writer builds each page image from (bytes, offsets), the bytes
-    // hx::ba_build_pages_host gives, and under Snappy compresses it with
+    // hx::ba_build_pages_host gives, cuts it by hx::ba_cut_pages under a
+    // limit, and under Snappy compresses each page with
     // hx::snappy_compress_host
     std::string err = hx::write_metric_sst_bytes(path, series, ts, bytes,
                                                  offsets, seqs, seq, n_rows,
-                                                 row_group, nullptr, codec);
+                                                 row_group, nullptr, codec,
+                                                 page_limit);
     if (!err.empty()) return fail(HX_ERR_IO, err);
     return HX_OK;
 }
@@ -3637,6 +3758,48 @@ extern "C" hx_status hx_debug_ba_pages(
     HIP_TRY(hipDeviceSynchronize());
     if (b.total())
         HIP_TRY(hipMemcpy(out, d_out, b.total(), hipMemcpyDeviceToHost));
+    return HX_OK;
+}
+
+// Kernel 1h and its twin over caller-built row_len: batch_sum gets
+// hx::ba_n_batches(n_out, row_group) words.
+static bool ba_batch_args_ok(const uint32_t* row_len, uint32_t n_out,
+                             uint32_t row_group, const uint64_t* batch_sum) {
+    return row_group != 0 && row_group <= hx::BA_MAX_ROW_GROUP &&
+           (!n_out || (row_len && batch_sum));
+}
+
+extern "C" hx_status hx_debug_ba_batch_sizes_host(const uint32_t* row_len,
+                                                  uint32_t n_out,
+                                                  uint32_t row_group,
+                                                  uint64_t* batch_sum) {
+    if (!ba_batch_args_ok(row_len, n_out, row_group, batch_sum))
+        return fail(HX_ERR_INVALID, "bad argument");
+    hx::ba_batch_sizes_host(row_len, n_out, row_group, batch_sum);
+    return HX_OK;
+}
+
+extern "C" hx_status hx_debug_ba_batch_sizes(const uint32_t* row_len,
+                                             uint32_t n_out,
+                                             uint32_t row_group,
+                                             uint64_t* batch_sum) {
+    if (!ba_batch_args_ok(row_len, n_out, row_group, batch_sum))
+        return fail(HX_ERR_INVALID, "bad argument");
+    const size_t n_b = hx::ba_n_batches(n_out, row_group);
+    if (n_b == 0) return HX_OK;
+    // every buffer exactly as large as the contract says it is
+    DevBufs dev;
+    uint32_t* d_len = nullptr;
+    unsigned long long* d_sum = nullptr;
+    HIP_TRY(dev.alloc((void**)&d_len, size_t(n_out) * 4));
+    HIP_TRY(dev.alloc((void**)&d_sum, n_b * 8));
+    HIP_TRY(hipMemcpy(d_len, row_len, size_t(n_out) * 4,
+                      hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(d_sum, 0xEE, n_b * 8));
+    HIP_TRY(hx::launch_ba_batch_sizes(nullptr, d_len, n_out, row_group,
+                                      d_sum));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(batch_sum, d_sum, n_b * 8, hipMemcpyDeviceToHost));
     return HX_OK;
 }
 
@@ -3718,6 +3881,7 @@ static hx_status gpu_write_bytes(const uint64_t* series, const int64_t* ts,
                                  const std::vector<uint64_t>& handles,
                                  int64_t n, std::vector<uint8_t>& host,
                                  std::vector<uint64_t>& page_off,
+                                 uint32_t page_limit, BaCuts& cuts,
                                  DeviceStreams* keys = nullptr,
                                  BaStreams* values = nullptr) {
     hipStream_t s = nullptr;
@@ -3755,8 +3919,12 @@ static hx_status gpu_write_bytes(const uint64_t* series, const int64_t* ts,
                                   (unsigned long long*)d_hs, (uint32_t)N));
     BaPageBuilder b;
     hx_status st = b.run(s, n_bytes, d_hs, nullptr, (uint32_t)N, (uint32_t)N,
-                         (uint32_t)kRowGroup);
+                         (uint32_t)kRowGroup, page_limit);
     if (st == HX_OK) st = b.verdict();
+    if (st != HX_OK) return st;
+    cuts = ba_cuts(b.batch_sum(), b.page_off.data(), b.n_pages, N,
+                   page_limit);
+    st = check_cuts(cuts, b.page_off.data(), b.n_pages);
     if (st != HX_OK) return st;
     const size_t key_bytes = 2 * N * 8;
     HIP_TRY(dev.alloc((void**)&d_final, key_bytes + b.total()));
@@ -3774,7 +3942,7 @@ static hx_status gpu_write_bytes(const uint64_t* series, const int64_t* ts,
         HIP_TRY(compress_ba_pages_device(s, d_final + key_bytes,
                                          page_off.data(), b.n_pages,
                                          b.d_words, b.d_row_len, (uint32_t)N,
-                                         false, *values));
+                                         cuts, false, *values));
         const int64_t col_words[5] = {0, (int64_t)N, -1, -1, -1};
         HIP_TRY(compress_columns_device(s, d_final, col_words, (uint32_t)N,
                                         nullptr, *keys));
@@ -3832,13 +4000,16 @@ extern "C" hx_status hx_write_bytes(hx_handle* h, const uint64_t* series,
     std::vector<uint64_t> page_off;
     const size_t N = (size_t)n;
     const int32_t codec = h->bytes_write_codec;
+    const uint32_t page_limit = h->bytes_page_limit;
+    BaCuts cuts;
     DeviceStreams key_streams;        // codec Snappy, device route
     BaStreams value_streams;          // codec Snappy, either route
     bool on_device = false;
     if (n >= (1 << 16) && hip_device_count() > 0) {
         on_device = codec == HX_CODEC_SNAPPY;
         st = gpu_write_bytes(series, ts, src, n_bytes, handles, n, host,
-                             page_off, on_device ? &key_streams : nullptr,
+                             page_off, page_limit, cuts,
+                             on_device ? &key_streams : nullptr,
                              on_device ? &value_streams : nullptr);
         if (st != HX_OK) return st;
     } else {
@@ -3859,6 +4030,14 @@ extern "C" hx_status hx_write_bytes(hx_handle* h, const uint64_t* series,
                                row_len.data(), page_off.data());
         st = check_page_sizes(page_off.data(), n_pages);
         if (st != HX_OK) return st;
+        std::vector<uint64_t> sums;
+        if (page_limit) {
+            sums.resize(hx::ba_n_batches(N, kRowGroup));
+            hx::ba_batch_sizes_host(row_len.data(), N, kRowGroup,
+                                    sums.data());
+        }
+        cuts = ba_cuts(page_limit ? sums.data() : nullptr, page_off.data(),
+                       (uint32_t)n_pages, N, page_limit);
         host.resize(2 * N * 8 + page_off[n_pages]);
         uint64_t* s2 = (uint64_t*)host.data();
         int64_t* t2 = (int64_t*)(host.data() + N * 8);
@@ -3871,7 +4050,7 @@ extern "C" hx_status hx_write_bytes(hx_handle* h, const uint64_t* series,
                                 host.data() + 2 * N * 8);
         if (codec == HX_CODEC_SNAPPY)
             ba_streams_host(host.data() + 2 * N * 8, page_off.data(),
-                            (uint32_t)n_pages, row_len.data(), N,
+                            (uint32_t)n_pages, row_len.data(), N, cuts,
                             value_streams);
     }
     uint64_t max_seq = 0;
@@ -3884,9 +4063,11 @@ extern "C" hx_status hx_write_bytes(hx_handle* h, const uint64_t* series,
     if (codec == HX_CODEC_SNAPPY) {
         // the key columns' streams (device route), then the value column's
         if (on_device) ready = key_streams.ready;
-        ba_ready_streams(ready, page_off.data(), n_pages32, value_streams);
+        ba_ready_streams(ready, page_off.data(), n_pages32, cuts,
+                         value_streams);
     } else {
-        ready = ba_ready(page_off.data(), n_pages32, host.data() + 2 * N * 8);
+        ready = ba_ready(page_off.data(), n_pages32, host.data() + 2 * N * 8,
+                         cuts);
     }
     std::string werr = hx::write_metric_sst_bytes(
         out_path, on_device ? nullptr : (const uint64_t*)host.data(),
@@ -4045,9 +4226,13 @@ static hx_status compact_rows_bytes(hx_handle* h, hx_prepared* P,
     }
     BaPageBuilder b;
     st = b.run(s, plan.blob_span, d_handles, d_gs, n, n_out,
-               (uint32_t)kRowGroup);
+               (uint32_t)kRowGroup, h->bytes_page_limit);
     if (st == HX_OK) st = b.verdict();
     if (st != HX_OK) return st;   // nothing written, nothing unlinked
+    const BaCuts cuts = ba_cuts(b.batch_sum(), b.page_off.data(), b.n_pages,
+                                n_out, h->bytes_page_limit);
+    st = check_cuts(cuts, b.page_off.data(), b.n_pages);
+    if (st != HX_OK) return st;
     const size_t n_keys = keep_seq ? 3 : 2;
     const size_t key_bytes = n_keys * size_t(n_out) * 8;
     uint8_t* d_final = nullptr;
@@ -4073,8 +4258,8 @@ static hx_status compact_rows_bytes(hx_handle* h, hx_prepared* P,
         DeviceStreams ks;
         HIP_TRY(compress_ba_pages_device(s, d_final + key_bytes,
                                          b.page_off.data(), b.n_pages,
-                                         b.d_words, b.d_row_len, n_out, timed,
-                                         vs));
+                                         b.d_words, b.d_row_len, n_out, cuts,
+                                         timed, vs));
         const int64_t col_words[5] = {
             0, (int64_t)n_out, -1, keep_seq ? 2 * (int64_t)n_out : -1, -1};
         HIP_TRY(compress_columns_device(s, d_final, col_words, n_out, nullptr,
@@ -4085,17 +4270,19 @@ static hx_status compact_rows_bytes(hx_handle* h, hx_prepared* P,
             size_t stream_bytes = vs.bytes.size();
             fprintf(stderr,
                     "[hx] compact_bytes rows=%u out_rows=%u append=%d "
-                    "keep_seq=%d pages=%u codec=snappy pages_ms=%.4f "
+                    "keep_seq=%d pages=%u data_pages=%u codec=snappy "
+                    "pages_ms=%.4f "
                     "stats_ms=%.4f compress_ms=%.4f value_stream_bytes=%zu "
                     "image_bytes=%zu decode_ms=%.4f d2h_bytes=%zu\n",
-                    n, n_out, int(append), int(keep_seq), b.n_pages, pages_ms,
-                    vs.stats_ms, vs.compress_ms, stream_bytes,
+                    n, n_out, int(append), int(keep_seq), b.n_pages, cuts.n(),
+                    pages_ms, vs.stats_ms, vs.compress_ms, stream_bytes,
                     size_t(b.total()), plan.decode_ms,
                     vs.d2h_bytes + ks.d2h_bytes +
-                        (size_t(b.n_pages) + 3) * 8 + (append ? 8 : 0) + 8);
+                        (size_t(b.n_pages) + 3 + b.n_batches) * 8 +
+                        (append ? 8 : 0) + 8);
         }
         std::vector<hx::PagePayload> ready = ks.ready;
-        ba_ready_streams(ready, b.page_off.data(), b.n_pages, vs);
+        ba_ready_streams(ready, b.page_off.data(), b.n_pages, cuts, vs);
         std::string werr = hx::write_metric_sst_bytes(
             out_path, nullptr, nullptr, nullptr, nullptr, nullptr, new_seq,
             n_out, kRowGroup, ready.data(), HX_CODEC_SNAPPY);
@@ -4114,12 +4301,13 @@ static hx_status compact_rows_bytes(hx_handle* h, hx_prepared* P,
                 "keep_seq=%d pages=%u pages_ms=%.4f decode_ms=%.4f "
                 "d2h_bytes=%zu\n",
                 n, n_out, int(append), int(keep_seq), b.n_pages, pages_ms,
-                plan.decode_ms, host.size() + (size_t(b.n_pages) + 3) * 8 +
+                plan.decode_ms,
+                host.size() + (size_t(b.n_pages) + 3 + b.n_batches) * 8 +
                     (append ? 8 : 0) + 8);
     }
 
     std::vector<hx::PagePayload> ready =
-        ba_ready(b.page_off.data(), b.n_pages, host.data() + key_bytes);
+        ba_ready(b.page_off.data(), b.n_pages, host.data() + key_bytes, cuts);
     const uint64_t* hk = (const uint64_t*)host.data();
     std::string werr = hx::write_metric_sst_bytes(
         out_path, hk, (const int64_t*)(hk + n_out), nullptr, nullptr,

@@ -121,3 +121,21 @@ extern "C" hx_status hx_debug_ba_page_minmax(
 extern "C" hx_status hx_debug_ba_page_minmax_host(
     const uint8_t* image, const uint64_t* page_off, const uint32_t* row_len,
     uint32_t n_out, uint32_t row_group, uint8_t* stats_out);
+
+// Debug: run kernel 1h (k_ba_batch_sizes; hx::ba_batch_sizes_host is its twin
+// in ba_pages.h) once over caller-built row_len on the current device, by the
+// production launch. row_len: n_out words as the size pass leaves them;
+// row_group <= 8192; batch_sum receives hx::ba_n_batches(n_out, row_group)
+// words: (ceil(n_out / row_group) - 1) * ceil(row_group / 1024) for the full
+// row groups plus ceil(rows of the last / 1024). The device output is
+// pre-filled with 0xEE and copied back whole. Every device buffer is exactly
+// as large as stated here. hx_debug_ba_batch_sizes_host is the same over the
+// host twin, no GPU needed.
+extern "C" hx_status hx_debug_ba_batch_sizes(const uint32_t* row_len,
+                                             uint32_t n_out,
+                                             uint32_t row_group,
+                                             uint64_t* batch_sum);
+extern "C" hx_status hx_debug_ba_batch_sizes_host(const uint32_t* row_len,
+                                                  uint32_t n_out,
+                                                  uint32_t row_group,
+                                                  uint64_t* batch_sum);

@@ -163,6 +163,12 @@ hipError_t launch_ba_build_pages(hipStream_t s, const uint8_t* src,
                                  const uint32_t* row_len,
                                  const unsigned long long* page_off,
                                  uint8_t* out);
+// Kernel 1h, one wave per 1024-row batch of every row group: batch_sum gets
+// hx::ba_n_batches(n_out, row_group) byte sums over row_len[n_out] as the
+// size pass left it (hx::ba_batch_sizes_host is the twin).
+hipError_t launch_ba_batch_sizes(hipStream_t s, const uint32_t* row_len,
+                                 uint32_t n_out, uint32_t row_group,
+                                 unsigned long long* batch_sum);
 // Kernel 1g, one workgroup per page of the image kernel 1f built (page_off
 // and row_len as its size pass left them): the chunk's footer statistics by
 // ba_pages.h's 65-byte rule, the bytes of hx::ba_page_minmax_host. out: one

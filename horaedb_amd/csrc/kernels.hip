@@ -3148,6 +3148,36 @@ k_ba_page_sizes(BaBuildParams B) {
     if (n_cap) atomicAdd(&B.counts[1], n_cap);
 }
 
+// Kernel 1h: the byte sum (4 + len per row, 4 for a refused row)
+// of every 1024-row batch of every row group, over the row_len the size pass
+// left — what hx::ba_cut_pages needs to cut a value chunk into data pages.
+// One wave per batch: 16 coalesced 4-byte loads per lane, a shuffle
+// reduction, one u64 store by lane 0. Reads row_len[0, n_out) only, writes
+// batch_sum[0, n_batches) only; no atomics. The sums equal
+// hx::ba_batch_sizes_host.
+__global__ void __launch_bounds__(256)
+k_ba_batch_sizes(const uint32_t* __restrict__ row_len, uint32_t n_out,
+                 uint32_t R, uint32_t per_group, uint32_t n_batches,
+                 unsigned long long* __restrict__ batch_sum) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6;
+    for (uint32_t b = wave; b < n_batches; b += n_waves) {
+        const uint64_t g = b / per_group, j = b % per_group;
+        const uint64_t r0 = g * R + j * BA_CUT_BATCH;
+        uint64_t r1 = r0 + BA_CUT_BATCH;
+        if (r1 > (g + 1) * R) r1 = (g + 1) * R;
+        if (r1 > n_out) r1 = n_out;
+        unsigned long long sum = 0;
+        for (uint64_t i = r0 + lane; i < r1; i += 64) {
+            const uint32_t l = row_len[i];
+            sum += 4ull + ((l & BA_ROW_SKIP) ? 0u : l);
+        }
+        for (int m = 32; m > 0; m >>= 1) sum += __shfl_xor(sum, m);
+        if (lane == 0) batch_sum[b] = sum;
+    }
+}
+
 // offs[i] = sum(size[0, i)), offs[n] = the total; k_snappy_scan's pattern.
 __global__ void __launch_bounds__(256)
 k_ba_page_scan(const unsigned long long* __restrict__ size, uint32_t n,
@@ -3984,6 +4014,22 @@ hipError_t launch_ba_build_pages(hipStream_t s, const uint8_t* src,
     hipLaunchKernelGGL(k_ba_build_pages,
                        dim3(n_pages > 65536u ? 65536u : n_pages), dim3(256),
                        0, s, B);
+    return hipGetLastError();
+}
+
+hipError_t launch_ba_batch_sizes(hipStream_t s, const uint32_t* row_len,
+                                 uint32_t n_out, uint32_t row_group,
+                                 unsigned long long* batch_sum) {
+    if (row_group == 0 || row_group > BA_MAX_ROW_GROUP)
+        return hipErrorInvalidValue;
+    const uint32_t n_b = (uint32_t)ba_n_batches(n_out, row_group);
+    if (n_b == 0) return hipSuccess;
+    const uint32_t blocks = (n_b + 3u) / 4u;   // four waves, a batch each
+    hipLaunchKernelGGL(k_ba_batch_sizes,
+                       dim3(blocks > 65536u ? 65536u : blocks), dim3(256), 0,
+                       s, row_len, n_out, row_group,
+                       (uint32_t)ba_batches_per_group(row_group), n_b,
+                       batch_sum);
     return hipGetLastError();
 }
 

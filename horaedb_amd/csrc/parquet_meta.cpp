@@ -283,4 +283,19 @@ bool select_pages(const uint8_t* buf, size_t len, int64_t base_off,
     return n_data == 1 && out->data.num_values == num_values;
 }
 
+void list_pages(const uint8_t* buf, size_t len, int64_t base_off,
+                int64_t num_values, bool optional_col, int32_t codec,
+                ChunkPageList* out) {
+    *out = ChunkPageList{};
+    for (const PageDesc& p :
+         walk_pages(buf, len, base_off, num_values, optional_col, codec)) {
+        if (p.page_type == 0 || p.page_type == 3) {
+            if (p.num_values != 0) out->data.push_back(p);
+        } else if (p.page_type == 2) {
+            out->dict = p;
+            out->has_dict = true;
+        }
+    }
+}
+
 }  // namespace hx

@@ -102,6 +102,20 @@ bool select_pages(const uint8_t* buf, size_t len, int64_t base_off,
                   int64_t num_values, bool optional_col, int32_t codec,
                   ChunkPages* out);
 
+// The same walk for a chunk that may hold several data pages (the BYTE_ARRAY
+// value chunk of a Binary store): every v1/v2 data page in file
+// order, pages of zero values left out, plus the dictionary page if there is
+// one. Throws like walk_pages. The caller checks that the pages' value
+// counts add up to the chunk's.
+struct ChunkPageList {
+    std::vector<PageDesc> data;
+    PageDesc dict{};
+    bool has_dict = false;
+};
+void list_pages(const uint8_t* buf, size_t len, int64_t base_off,
+                int64_t num_values, bool optional_col, int32_t codec,
+                ChunkPageList* out);
+
 // little-endian i64 from an 8-byte statistics value
 int64_t stat_i64(const std::string& s);
 

@@ -286,6 +286,61 @@ struct PageWriter {
     }
 };
 
+// A BYTE_ARRAY chunk of several v1 PLAIN data pages back to back (DESIGN
+// §10): page i holds rows[i] values and ulen[i] uncompressed bytes, the
+// consecutive slices of `image` (may be null when every stream is given).
+// streams (snappy only, may be null): the pages' Snappy streams back to back,
+// slen[i] bytes each; otherwise each slice is compressed here. m gets the
+// first page's offset and the sums over all headers and payloads.
+bool write_ba_pages(FILE* f, bool snappy, uint32_t k, const uint32_t* rows,
+                    const uint32_t* ulen, const uint8_t* image,
+                    const uint8_t* streams, const uint32_t* slen,
+                    int64_t& off, ChunkMeta& m) {
+    m.data_page_offset = off;
+    m.codec = snappy ? 1 : 0;
+    m.total_size = 0;
+    m.total_compressed = 0;
+    std::vector<uint8_t> comp;
+    size_t at = 0, s_at = 0;
+    for (uint32_t i = 0; i < k; i++) {
+        const uint8_t* out = image ? image + at : nullptr;
+        size_t out_len = ulen[i];
+        if (snappy && streams) {
+            out = streams + s_at;
+            out_len = slen[i];
+            s_at += slen[i];
+        } else if (snappy) {
+            comp.resize(size_t(snappy_max_compressed(ulen[i])));
+            comp.resize(snappy_compress_host(image + at, ulen[i], comp.data(),
+                                             comp.size()));
+            out = comp.data();
+            out_len = comp.size();
+        }
+        auto hdr = page_header(int32_t(rows[i]), int32_t(ulen[i]),
+                               int32_t(out_len));
+        if (fwrite(hdr.data(), 1, hdr.size(), f) != hdr.size()) return false;
+        if (out_len && fwrite(out, 1, out_len, f) != out_len) return false;
+        m.total_size += int64_t(hdr.size() + ulen[i]);
+        m.total_compressed += int64_t(hdr.size() + out_len);
+        at += ulen[i];
+    }
+    off += m.total_compressed;
+    return true;
+}
+
+// the cuts a ready entry brought: they must add up to rows and bytes
+bool split_ok(const PagePayload& r, int64_t rows, uint64_t bytes) {
+    if (!r.split_rows || !r.split_ulen) return false;
+    uint64_t sr = 0, sb = 0;
+    for (uint32_t i = 0; i < r.n_split; i++) {
+        if (r.split_rows[i] == 0 || r.split_ulen[i] > 0x7FFFFFFFu)
+            return false;
+        sr += r.split_rows[i];
+        sb += r.split_ulen[i];
+    }
+    return sr == uint64_t(rows) && sb == bytes;
+}
+
 // Statistics a ready page brought along; false = compute from the column.
 bool stats_from_ready(const PagePayload* ready, int64_t idx, ChunkMeta& m) {
     if (!ready || !ready[idx].ptr || ready[idx].stats == 0) return false;
@@ -506,8 +561,10 @@ std::string write_metric_sst_nullable(const std::string& path,
 std::string write_table_sst(const std::string& path, const WriterCol* cols,
                             int32_t n_cols, int64_t n, int64_t row_group,
                             int32_t codec, const PagePayload* ready,
-                            int32_t ba_codec) {
+                            int32_t ba_codec, uint32_t ba_page_limit) {
     if (n <= 0 || n_cols <= 0) return "write_table_sst: no rows/cols";
+    if (ba_page_limit > BA_PAGE_LIMIT_MAX)
+        return "write_table_sst: page limit above 2^30";
     if ((codec != 0 && codec != 1) || (ba_codec != 0 && ba_codec != 1))
         return "write_table_sst: unknown codec";
     FILE* f = fopen(path.c_str(), "wb");
@@ -533,6 +590,8 @@ std::string write_table_sst(const std::string& path, const WriterCol* cols,
     };
     std::vector<RG> rgs;
     std::vector<uint8_t> payload;
+    std::vector<uint32_t> cut_rows, cut_ulen, cut_len;
+    std::vector<uint64_t> cut_sums, cut_bytes;
     PageWriter pw(codec, ready, n_cols);
     for (int64_t g = 0, base = 0; base < n; g++, base += row_group) {
         int64_t rows = std::min<int64_t>(row_group, n - base);
@@ -565,14 +624,40 @@ std::string write_table_sst(const std::string& path, const WriterCol* cols,
                     m.has_stats = bs->has != 0;
                     m.mn.assign((const char*)bs->min, bs->min_len);
                     m.mx.assign((const char*)bs->max, bs->max_len);
+                    if (r6->n_split > 1) {
+                        uint64_t sl = 0;
+                        for (uint32_t i = 0; r6->split_len && i < r6->n_split;
+                             i++)
+                            sl += r6->split_len[i];
+                        if (!split_ok(*r6, rows, r6->ulen) ||
+                            !r6->split_len || sl != r6->len)
+                            return fail("write_table_sst: a ready BYTE_ARRAY "
+                                        "entry's page cuts do not add up");
+                        if (!write_ba_pages(f, true, r6->n_split,
+                                            r6->split_rows, r6->split_ulen,
+                                            nullptr, r6->ptr, r6->split_len,
+                                            off, m))
+                            return fail("write failed");
+                        continue;
+                    }
                     if (!pw.write(f, g, c, true, (int32_t)rows, nullptr, 0,
                                   nullptr, r6->ulen, off, m))
                         return fail("write failed");
                     continue;
                 }
+                uint32_t n_cut = 0;
+                const uint32_t *cr_ = nullptr, *cu_ = nullptr;
                 if (r6) {
                     body = r6->ptr;
                     body_len = r6->len;
+                    if (r6->n_split > 1) {
+                        if (!split_ok(*r6, rows, r6->len))
+                            return fail("write_table_sst: a ready BYTE_ARRAY "
+                                        "entry's page cuts do not add up");
+                        n_cut = r6->n_split;
+                        cr_ = r6->split_rows;
+                        cu_ = r6->split_ulen;
+                    }
                 } else {
                     if (!wc.offsets)
                         return fail("write_table_sst: BYTE_ARRAY needs "
@@ -590,6 +675,27 @@ std::string write_table_sst(const std::string& path, const WriterCol* cols,
                     }
                     body = payload.data();
                     body_len = payload.size();
+                    if (ba_page_limit && payload.size() <= 0x7FFFFFFFull) {
+                        // the cut rule over this row group's rows
+                        cut_len.resize(size_t(rows));
+                        for (int64_t r = 0; r < rows; r++)
+                            cut_len[r] = uint32_t(wc.offsets[base + r + 1] -
+                                                  wc.offsets[base + r]);
+                        const size_t nb = size_t(ba_n_batches(rows, rows));
+                        cut_sums.resize(nb);
+                        cut_bytes.resize(nb);
+                        cut_rows.resize(nb);
+                        cut_ulen.resize(nb);
+                        ba_batch_sizes_host(cut_len.data(), uint64_t(rows),
+                                            uint64_t(rows), cut_sums.data());
+                        n_cut = ba_cut_pages(cut_sums.data(), uint64_t(rows),
+                                             ba_page_limit, cut_rows.data(),
+                                             cut_bytes.data());
+                        for (uint32_t i = 0; i < n_cut; i++)
+                            cut_ulen[i] = uint32_t(cut_bytes[i]);
+                        cr_ = cut_rows.data();
+                        cu_ = cut_ulen.data();
+                    }
                 }
                 if (body_len > 0x7FFFFFFFull)
                     return fail("write_table_sst: BYTE_ARRAY page image "
@@ -622,6 +728,12 @@ std::string write_table_sst(const std::string& path, const WriterCol* cols,
                 m.has_stats = mn_len <= 64 && mx_len <= 64;
                 m.mn.assign((const char*)mn, mn_len);
                 m.mx.assign((const char*)mx, mx_len);
+                if (n_cut > 1) {
+                    if (!write_ba_pages(f, ba_codec == 1, n_cut, cr_, cu_,
+                                        body, nullptr, nullptr, off, m))
+                        return fail("write failed");
+                    continue;
+                }
             } else {
                 if (!column_present(wc.data, ready, g * n_cols + c, codec))
                     return fail("write_table_sst: column neither given nor "
@@ -722,7 +834,8 @@ std::string write_metric_sst_bytes(const std::string& path,
                                    const int64_t* offsets,
                                    const uint64_t* seqs, uint64_t seq,
                                    int64_t n, int64_t row_group,
-                                   const PagePayload* ready, int32_t codec) {
+                                   const PagePayload* ready, int32_t codec,
+                                   uint32_t page_limit) {
     if (n <= 0) return "write_metric_sst_bytes: no rows";
     std::vector<uint64_t> zeros(n, 0), seq_col;
     if (!seqs) {
@@ -736,7 +849,8 @@ std::string write_metric_sst_bytes(const std::string& path,
         {"__seq__", 2, 14, seqs, nullptr},
         {"__reserved__", 2, 14, zeros.data(), nullptr},
     };
-    return write_table_sst(path, cols, 5, n, row_group, codec, ready, codec);
+    return write_table_sst(path, cols, 5, n, row_group, codec, ready, codec,
+                           page_limit);
 }
 
 }  // namespace hx

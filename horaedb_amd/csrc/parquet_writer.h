@@ -45,6 +45,18 @@ struct PagePayload {
     // BYTE_ARRAY stream entries (ba_codec 1) only
     uint32_t ulen = 0;                     // uncompressed page size
     const BaPageStat* ba_stat = nullptr;   // the chunk's statistics
+    // A BYTE_ARRAY entry cut into n_split data pages (hx::ba_cut_pages; 0 or 1
+    // = one page, every field above as it always was). split_rows and
+    // split_ulen give each page's rows and uncompressed bytes; they add up to
+    // the chunk's rows and to the whole image (len under ba_codec 0, ulen
+    // under ba_codec 1). Under ba_codec 0 ptr is still the one image and the
+    // pages are its consecutive slices; under ba_codec 1 ptr holds the
+    // pages' streams back to back, split_len bytes each (len = their sum),
+    // each the twin's stream of its slice.
+    uint32_t n_split = 0;
+    const uint32_t* split_rows = nullptr;
+    const uint32_t* split_ulen = nullptr;
+    const uint32_t* split_len = nullptr;
 };
 
 // columns are caller-provided arrays of n rows; seq is constant per file
@@ -100,7 +112,8 @@ std::string write_table_sst(const std::string& path, const WriterCol* cols,
                             int32_t n_cols, int64_t n, int64_t row_group,
                             int32_t codec = 0,
                             const PagePayload* ready = nullptr,
-                            int32_t ba_codec = 0);
+                            int32_t ba_codec = 0,
+                            uint32_t ba_page_limit = 0);
 
 // per-row variable-length seq variant of the metric writer (general
 // compaction outputs, executor.rs:155-222 keep_builtin path)
@@ -127,7 +140,10 @@ std::string write_metric_sst_seqs(const std::string& path,
 // stream with ulen and ba_stat (PagePayload). Statistics are the
 // lexicographic min/max of the page's values, omitted above 64 B, so the file
 // is a pure function of the rows and the codec whichever route built the
-// pages.
+// pages. page_limit (0 = one data page per chunk, the file it always wrote;
+// else at most BA_PAGE_LIMIT_MAX) cuts a value image built here from (bytes,
+// offsets) into data pages by hx::ba_cut_pages; a ready entry brings its own
+// cuts (PagePayload::n_split) and the limit does not touch it.
 std::string write_metric_sst_bytes(const std::string& path,
                                    const uint64_t* series, const int64_t* ts,
                                    const uint8_t* bytes,
@@ -135,6 +151,7 @@ std::string write_metric_sst_bytes(const std::string& path,
                                    const uint64_t* seqs, uint64_t seq,
                                    int64_t n, int64_t row_group,
                                    const PagePayload* ready = nullptr,
-                                   int32_t codec = 0);
+                                   int32_t codec = 0,
+                                   uint32_t page_limit = 0);
 
 }  // namespace hx

@@ -205,23 +205,256 @@ StageStatus stage_dictionary(const uint8_t* buf, const ChunkRef& cr,
 }
 
 
+const char* const kBytesPlainOnly =
+    "byte value columns support PLAIN pages only (uncompressed, Snappy, Zstd)";
+
 // Binary value column (BytesMergeOperator stores, operator.rs:47-111): the
 // PLAIN BYTE_ARRAY payload stays in the blob; per-row handles (off << 20 |
 // len) are walked by k_ba_offsets into the SST's handle array at decode time.
 // A handle is relative to the blob, so the body must be in the blob's own
-// offset space: uncompressed, Zstd (decompressed in place) and stored Snappy
-// pages sit in their slot, any other Snappy page is decoded into the blob's
-// tail (stage_chunk.h), never into dec.
-void stage_bytes_value(const ChunkRef& cr, const ChunkRole& role,
-                       const Body& body, StagedPages& pages, ChunkResult& res) {
-    BaPageDesc bp{};
-    bp.src_off = body.off;   // blob byte offset (no flag bit)
-    bp.src_len = body.raw;
-    bp.n_values = (uint32_t)cr.num_values;
-    bp.first_row = int64_t(role.bytes_handles / 8) + role.row_base;
-    pages.ba.push_back(bp);
+// offset space: uncompressed, Zstd (inflated into the slot) and stored Snappy
+// pages sit in their slot — stored meaning one literal, placed verbatim, or
+// several literals and nothing else (the Snappy library's form above one
+// 64 KiB fragment), whose bodies staging lays end to end — and any other
+// Snappy page is decoded into the blob's tail (stage_chunk.h), never into
+// dec.
+//
+// The chunk may hold any number of data pages (parquet-rs and arrow-cpp close
+// a page once it reaches 1 MiB). Every page is staged by the one
+// set of rules; the pages share the chunk's slot at cumulative offsets and
+// each gets a BaPageDesc of its own, first_row advanced by the rows of the
+// pages before it. The first page sits where a lone page always sat (slot
+// start; a stored literal shifted until its body is 64-aligned); a later page
+// starts at the next 8-byte boundary, which the k_snappy_decompress word
+// loads of a tail page's stream need and which a page header (17 bytes at the
+// least) always pays for. Nothing is reserved or appended before every page
+// that can be judged without its Zstd inflate has been judged, and the tail
+// is claimed in one piece.
+StageStatus stage_bytes_chunk(const uint8_t* buf, const ChunkRef& cr,
+                              const ChunkRole& role, const ChunkSlot& slot,
+                              StagedPages& pages, ChunkResult& res,
+                              std::atomic<size_t>* tail) {
+    ChunkPageList pl;
+    try {
+        list_pages(buf, size_t(cr.comp_size), cr.chunk_start, cr.num_values,
+                   !cr.required, cr.codec, &pl);
+    } catch (const std::exception& e) {
+        return bad(HX_ERR_FORMAT, e.what());
+    }
+    if (pl.data.empty())
+        return bad(HX_ERR_UNSUPPORTED,
+                   "expected one data page per chunk (row-group 8192 "
+                   "writer contract)");
+    int64_t total_values = 0;
+    for (const PageDesc& dp : pl.data) {
+        if (dp.num_values < 0)
+            return bad(HX_ERR_FORMAT, "negative value count");
+        total_values += dp.num_values;
+    }
+    if (total_values != cr.num_values)
+        return bad(HX_ERR_FORMAT,
+                   "data pages hold " + std::to_string(total_values) +
+                       " values, the chunk declares " +
+                       std::to_string(cr.num_values));
+    if (cr.codec != CODEC_UNCOMPRESSED && cr.codec != CODEC_SNAPPY &&
+        cr.codec != CODEC_ZSTD)
+        return bad(HX_ERR_UNSUPPORTED,
+                   "codec unsupported (uncompressed, Snappy and Zstd)");
+    if (cr.codec == CODEC_ZSTD && !zstd().ok)
+        return bad(HX_ERR_UNSUPPORTED,
+                   "Zstd pages but libzstd.so.1 is not loadable");
+    const size_t words = (size_t(cr.num_values) + 63) / 64;
+    if (slot.bitmap && slot.bitmap_cap < words * 8)
+        return bad(HX_ERR_INVALID, "bitmap capacity too small");
+    const bool lone = pl.data.size() == 1;
+
+    // the levels of one page: decoded, never trusted to the statistics; any
+    // null refuses the chunk. *lvl = level bytes that open the DEcompressed
+    // body of a compressed v1 page.
+    auto check_levels = [&](const PageDesc& dp, const uint8_t* page,
+                            const uint8_t* post, size_t post_len,
+                            uint32_t* lvl) {
+        uint32_t n_valid = 0;
+        std::string why = page_levels(dp, cr.codec, page, post, post_len,
+                                      lone ? slot.bitmap : nullptr, lvl,
+                                      &n_valid);
+        hx_status st = HX_ERR_FORMAT;
+        if (why.empty() && int64_t(n_valid) != int64_t(dp.num_values)) {
+            why = null_policy(int64_t(dp.num_values) - int64_t(n_valid), role,
+                              dp.encoding);
+            st = HX_ERR_UNSUPPORTED;
+        }
+        res.level_bytes += *lvl ? *lvl : uint32_t(dp.def_level_bytes);
+        if (why.empty()) return StageStatus{};
+        return bad(st, std::string("column ") + kColNames[role.col] + ": " +
+                           why);
+    };
+
+    // ---- pass 1: judge every page, place nothing ------------------------
+    struct Plan {
+        size_t in_chunk, payload, ulen;
+        bool zstd_page, snappy_page, stored, literals, to_tail;
+        uint32_t lvl, body_off;
+    };
+    std::vector<Plan> plan(pl.data.size());
+    uint64_t tail_claim = 0, tail_need = 0;
+    for (size_t k = 0; k < pl.data.size(); k++) {
+        const PageDesc& dp = pl.data[k];
+        Plan& p = plan[k];
+        p = Plan{};
+        p.in_chunk = size_t(dp.payload_off - cr.chunk_start);
+        // size sanity BEFORE any copy (walk_pages validates too; this guards
+        // the invariants the code below depends on)
+        if (dp.def_level_bytes < 0 || dp.def_level_bytes > dp.compressed_size ||
+            dp.def_level_bytes > dp.uncompressed_size ||
+            dp.payload_off < cr.chunk_start ||
+            p.in_chunk + size_t(dp.compressed_size) > size_t(cr.comp_size))
+            return bad(HX_ERR_FORMAT, "page size fields out of bounds");
+        const uint8_t* page = buf + p.in_chunk;
+        const uint8_t* src = page + dp.def_level_bytes;
+        p.payload = size_t(dp.compressed_size) - size_t(dp.def_level_bytes);
+        p.ulen = size_t(dp.uncompressed_size) - size_t(dp.def_level_bytes);
+        p.zstd_page = cr.codec == CODEC_ZSTD && dp.is_compressed;
+        p.snappy_page = cr.codec == CODEC_SNAPPY && dp.is_compressed;
+        // Zstd v1 pages are looked at after the inflate
+        if (!cr.required && !(p.zstd_page && dp.levels_in_stream)) {
+            StageStatus s = check_levels(dp, page, nullptr, 0, &p.lvl);
+            if (!s.ok()) return s;
+        }
+        if (p.snappy_page && dp.encoding == ENC_PLAIN &&
+            hx_snappy_stored_literal(src, p.payload, (uint32_t)p.ulen,
+                                     &p.body_off)) {
+            p.stored = true;
+        } else if (p.snappy_page && dp.encoding == ENC_PLAIN &&
+                   hx_snappy_literals_only(src, p.payload, (uint32_t)p.ulen,
+                                           nullptr)) {
+            // several literals and nothing else: the Snappy library's form
+            // of an incompressible page above one 64 KiB fragment
+            p.literals = true;
+        } else if (p.snappy_page && p.ulen != 0) {
+            if (dp.encoding != ENC_PLAIN || !tail)
+                return bad(HX_ERR_UNSUPPORTED, kBytesPlainOnly);
+            p.to_tail = true;
+            tail_claim += p.ulen;
+            tail_need += align64(p.ulen);
+        }
+        if (dp.encoding != ENC_PLAIN && !p.zstd_page)
+            return bad(HX_ERR_UNSUPPORTED, kBytesPlainOnly);
+    }
+    // the chunk's declared size bounds what its pages may claim of the tail,
+    // before anything is reserved
+    if (tail_claim &&
+        (cr.uncomp_size < 0 || tail_claim > uint64_t(cr.uncomp_size)))
+        return bad(HX_ERR_FORMAT, kTooLarge);
+
+    // ---- pass 2: place the pages ----------------------------------------
+    std::vector<BaPageDesc> ba;
+    std::vector<SnappyPageDesc> sn;
+    uint64_t in_place = 0, in_place_bytes = 0, raw_total = 0;
+    size_t at = 0;                 // cursor in the slot
+    size_t tail_at = 0;
+    bool tail_taken = false;
+    int64_t first_row = int64_t(role.bytes_handles / 8) + role.row_base;
+    for (size_t k = 0; k < pl.data.size(); k++) {
+        const PageDesc& dp = pl.data[k];
+        Plan& p = plan[k];
+        const uint8_t* src = buf + p.in_chunk + dp.def_level_bytes;
+        if (k) at = (at + 7) & ~size_t(7);
+        Body body{slot.off + at, p.payload, 0};
+        if (p.zstd_page) {
+            // host-side inflate from the read buffer into the slot
+            StageStatus s =
+                slot_inflate(slot, at, p.ulen, src, p.payload, "page");
+            if (!s.ok()) return s;
+            body.raw = p.ulen;
+            if (!cr.required && dp.levels_in_stream) {
+                // drop the level block: the body moves to where the page
+                // starts, as for a REQUIRED page
+                s = check_levels(dp, buf + p.in_chunk, slot.base + at, p.ulen,
+                                 &p.lvl);
+                if (!s.ok()) return s;
+                std::memmove(slot.base + at, slot.base + at + p.lvl,
+                             p.ulen - p.lvl);
+                body.raw = p.ulen - p.lvl;
+            }
+            if (dp.encoding != ENC_PLAIN)
+                return bad(HX_ERR_UNSUPPORTED, kBytesPlainOnly);
+            at += body.raw;
+        } else if (p.stored) {
+            // nothing to decode: the payload goes in verbatim and the
+            // descriptor points at the literal's body (behind an OPTIONAL v1
+            // page's level block). A lone or first page is shifted so that
+            // body is 64-aligned, as it always was.
+            const uint32_t body_off = p.body_off + p.lvl;
+            const size_t pad = k ? 0 : (64 - (body_off & 63u)) & 63u;
+            if (!slot_put(slot, at + pad, src, p.payload))
+                return bad(HX_ERR_FORMAT, kTooLarge);
+            body = Body{slot.off + at + pad + body_off, p.ulen - p.lvl, 0};
+            in_place++;
+            in_place_bytes += body.raw;
+            at += pad + p.payload;
+        } else if (p.literals) {
+            // nothing to decode either: the literals' bodies go into the
+            // slot back to back (ulen < payload, so they fit where the
+            // payload would), the tags between them dropped, and the page is
+            // read in place like a stored one
+            const size_t pad = k ? 0 : (64 - (p.lvl & 63u)) & 63u;
+            if (!slot_fits(slot, at + pad, p.ulen) ||
+                !hx_snappy_literals_only(src, p.payload, (uint32_t)p.ulen,
+                                         slot.base + at + pad))
+                return bad(HX_ERR_FORMAT, kTooLarge);
+            body = Body{slot.off + at + pad + p.lvl, p.ulen - p.lvl, 0};
+            in_place++;
+            in_place_bytes += body.raw;
+            at += pad + p.ulen;
+        } else {
+            if (!slot_put(slot, at, src, p.payload))
+                return bad(HX_ERR_FORMAT, kTooLarge);
+            if (p.snappy_page && p.ulen == 0) {
+                body.raw = 0;   // v2 page of nulls only: nothing to decode
+            } else if (p.to_tail) {
+                // decoded into the blob's tail, so the handles k_ba_offsets
+                // writes stay relative to the blob
+                if (!tail_taken) {
+                    tail_at = tail->fetch_add(size_t(tail_need));
+                    tail_taken = true;
+                }
+                SnappyPageDesc sp{};
+                sp.src_off = slot.off + at;
+                sp.comp_len = (uint32_t)p.payload;
+                sp.uncomp_len = (uint32_t)p.ulen;
+                sp.dst_off = tail_at;
+                tail_at += align64(p.ulen);
+                sn.push_back(sp);
+                body.off = sp.dst_off + p.lvl;
+                body.raw = p.ulen - p.lvl;
+            }
+            at += p.payload;
+        }
+        BaPageDesc bp{};
+        bp.src_off = body.off;   // blob byte offset (no flag bit)
+        bp.src_len = body.raw;
+        bp.n_values = (uint32_t)dp.num_values;
+        bp.first_row = first_row;
+        first_row += dp.num_values;
+        ba.push_back(bp);
+        raw_total += body.raw;
+    }
+    if (!lone && slot.bitmap && !cr.required) {
+        // no page held a null
+        std::memset(slot.bitmap, 0, words * 8);
+        hx_bitmap_set_range(slot.bitmap, 0, uint64_t(cr.num_values));
+    }
+    pages.ba.insert(pages.ba.end(), ba.begin(), ba.end());
+    pages.snappy_ba.insert(pages.snappy_ba.end(), sn.begin(), sn.end());
+    pages.pages_in_place += in_place;
+    pages.bytes_in_place += in_place_bytes;
+    res.n_valid = (uint32_t)cr.num_values;
+    res.stored = in_place == pl.data.size();
+    res.raw_size = raw_total;
     res.final_off =
         OFF_DEC | (role.bytes_handles + uint64_t(role.row_base) * 8);
+    return {};
 }
 
 // PLAIN 8-byte column: read where it is, unless it sits behind a level block
@@ -282,6 +515,9 @@ StageStatus stage_chunk(const uint8_t* buf, const ChunkRef& cr,
                         std::atomic<size_t>& dec, StagedPages& pages,
                         ChunkResult& res, std::atomic<size_t>* tail) {
     res = ChunkResult{};
+    // the BYTE_ARRAY value chunk of a Binary store: any number of data pages
+    if (role.bytes_value && role.col == 2)
+        return stage_bytes_chunk(buf, cr, role, slot, pages, res, tail);
     // layout contract: exactly one v1/v2 data page per chunk, plus an
     // optional dictionary page (RLE_DICTIONARY chunks)
     ChunkPages cp;
@@ -323,7 +559,6 @@ StageStatus stage_chunk(const uint8_t* buf, const ChunkRef& cr,
     // size of the page body once decompressed
     const size_t ulen =
         size_t(dp.uncompressed_size) - size_t(dp.def_level_bytes);
-    const bool value_bytes = role.bytes_value && role.col == 2;
     const bool zstd_page = cr.codec == CODEC_ZSTD && dp.is_compressed;
     const bool snappy_page = cr.codec == CODEC_SNAPPY && dp.is_compressed;
     Body body{slot.off, payload, 0};
@@ -396,25 +631,6 @@ StageStatus stage_chunk(const uint8_t* buf, const ChunkRef& cr,
             return bad(HX_ERR_FORMAT, kTooLarge);
         if (snappy_page && ulen == 0) {
             body.raw = 0;   // v2 page of nulls only: nothing to decode
-        } else if (snappy_page && value_bytes) {
-            // decoded into the blob's tail, so the handles k_ba_offsets
-            // writes stay relative to the blob
-            if (dp.encoding != ENC_PLAIN || !tail)
-                return bad(HX_ERR_UNSUPPORTED,
-                           "byte value columns support PLAIN pages only "
-                           "(uncompressed, Snappy, Zstd)");
-            // the chunk's declared size bounds what a page may claim, before
-            // anything is reserved
-            if (cr.uncomp_size < 0 || uint64_t(ulen) > uint64_t(cr.uncomp_size))
-                return bad(HX_ERR_FORMAT, kTooLarge);
-            SnappyPageDesc sp{};
-            sp.src_off = slot.off;
-            sp.comp_len = (uint32_t)payload;
-            sp.uncomp_len = (uint32_t)ulen;
-            sp.dst_off = tail->fetch_add(align64(ulen));
-            pages.snappy_ba.push_back(sp);
-            body.off = sp.dst_off + body.lvl;
-            body.raw = ulen - body.lvl;
         } else if (snappy_page) {
             SnappyPageDesc sp{};
             sp.src_off = slot.off;
@@ -430,14 +646,6 @@ StageStatus stage_chunk(const uint8_t* buf, const ChunkRef& cr,
     }
     res.raw_size = body.raw;
 
-    if (value_bytes) {
-        if (dp.encoding != ENC_PLAIN)
-            return bad(HX_ERR_UNSUPPORTED,
-                       "byte value columns support PLAIN pages only "
-                       "(uncompressed, Snappy, Zstd)");
-        stage_bytes_value(cr, role, body, pages, res);
-        return {};
-    }
     if (dp.encoding == ENC_PLAIN)
         return stage_plain(cr, body, dec, pages, res);
     if (dp.encoding == ENC_DELTA_BINARY_PACKED && role.col != 2)

@@ -87,7 +87,10 @@ struct StagedPages {
     uint64_t bytes_in_place = 0;
 };
 
-// What the plan keeps of one staged chunk.
+// What the plan keeps of one staged chunk. For the BYTE_ARRAY value chunk of
+// a Binary store, which may hold several data pages: n_valid is the chunk's
+// value count, level_bytes and raw_size are sums over its pages, stored says
+// that every page is a stored Snappy page.
 struct ChunkResult {
     uint64_t final_off = 0;   // RgDesc column offset (blob, or OFF_DEC | dec)
     bool has_nulls = false;   // the page holds nulls: its validity words
@@ -118,6 +121,17 @@ StageStatus read_chunk(int fd, const std::string& path, const ChunkRef& cr,
 // value column that is no stored literal reserves align64(uncomp_len) there
 // and is decoded to that place, so its handles stay relative to the blob;
 // without a cursor such a page is refused.
+// The 8-byte columns hold exactly one data page per chunk (plus at most one
+// dictionary page). The BYTE_ARRAY value chunk of a Binary store
+// (role.bytes_value && role.col == 2) may hold any number: each page is
+// staged by the same rules into the chunk's one slot at cumulative offsets
+// (chunk_reserve covers them: a later page starts 8-aligned, paid for by its
+// header) and gets a BaPageDesc of its own, first_row advanced by the rows
+// of the pages before it; a tail page gets its own SnappyPageDesc. Page
+// value counts that do not add up to cr.num_values are HX_ERR_FORMAT, a page
+// of zero values is skipped, a null in any page refuses the chunk, and the
+// tail pages' cumulative claim is checked against cr.uncomp_size before
+// anything is reserved or appended.
 StageStatus stage_chunk(const uint8_t* buf, const ChunkRef& cr,
                         const ChunkRole& role, const ChunkSlot& slot,
                         std::atomic<size_t>& dec, StagedPages& pages,

@@ -150,6 +150,12 @@ def _load():
     lib.hx_write_sst_bytes_codec.argtypes = \
         lib.hx_write_sst_bytes.argtypes + [C.c_int32]
     lib.hx_set_bytes_write_codec.argtypes = [C.c_void_p, C.c_int32]
+    lib.hx_write_sst_bytes_paged.argtypes = \
+        lib.hx_write_sst_bytes_codec.argtypes + [C.c_uint32]
+    lib.hx_set_bytes_page_limit.argtypes = [C.c_void_p, C.c_uint32]
+    for f in (lib.hx_debug_ba_batch_sizes, lib.hx_debug_ba_batch_sizes_host):
+        f.argtypes = [C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32,
+                      C.POINTER(C.c_uint64)]
     for f in (lib.hx_debug_ba_page_minmax, lib.hx_debug_ba_page_minmax_host):
         f.argtypes = [C.c_void_p, C.POINTER(C.c_uint64),
                       C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32,
@@ -485,6 +491,17 @@ class Store:
         write_bytes, compact and compact_files write from now on."""
         _check(_lib.hx_set_bytes_write_codec(self._h, int(codec)))
 
+    def set_bytes_page_limit(self, limit):
+        """Writer setting of a Binary store (hx_set_bytes_page_limit): 0
+        (default, one data page per value chunk) or 1 .. 2**30 bytes, the
+        size at which write_bytes, compact and compact_files close a data
+        page of a value chunk; BYTES_PAGE_LIMIT_REFERENCE is the reference
+        writers' 1 MiB."""
+        limit = int(limit)
+        if not 0 <= limit < 2 ** 32:
+            raise HxError(6, "bytes page limit: 0 or 1 .. 2^30")
+        _check(_lib.hx_set_bytes_page_limit(self._h, limit))
+
     def write(self, series, ts, value, enable_check=True, valid=None):
         """ColumnarStorage::write (storage.rs:76-89): stable PK sort + new
         SST + catalog add. Returns the new file's sequence. valid: bool
@@ -655,11 +672,13 @@ def _bytes_col(values, n):
 
 
 def write_sst_native_bytes(path, series, ts, values, seq, seqs=None,
-                           row_group=8192, codec=0):
+                           row_group=8192, codec=0, page_limit=None):
     """GPU-free writer of one Binary-value SST (hx_write_sst_bytes), rows in
     the order given. seqs: per-row __seq__ values, or None for the constant
     seq. codec: CODEC_NONE (default, the old entry) or CODEC_SNAPPY
-    (hx_write_sst_bytes_codec)."""
+    (hx_write_sst_bytes_codec). page_limit: None (the entries above), or the
+    data-page limit of the value chunks (hx_write_sst_bytes_paged; 0 = one
+    page per chunk)."""
     series = np.ascontiguousarray(series, dtype=np.uint64)
     ts = np.ascontiguousarray(ts, dtype=np.int64)
     n = len(series)
@@ -670,7 +689,12 @@ def write_sst_native_bytes(path, series, ts, values, seq, seqs=None,
             offs.ctypes.data_as(C.POINTER(C.c_int64)),
             None if sq is None else sq.ctypes.data_as(C.POINTER(C.c_uint64)),
             int(seq), n, row_group)
-    if codec:
+    if page_limit is not None:
+        if not 0 <= int(page_limit) < 2 ** 32:
+            raise HxError(6, "bytes page limit: 0 or 1 .. 2^30")
+        _check(_lib.hx_write_sst_bytes_paged(*args, int(codec),
+                                             int(page_limit)))
+    elif codec:
         _check(_lib.hx_write_sst_bytes_codec(*args, int(codec)))
     else:
         _check(_lib.hx_write_sst_bytes(*args))
@@ -781,6 +805,41 @@ def ba_page_minmax_device(values, row_group=8192, skip=()):
     Arguments and result as ba_page_minmax_host."""
     return _ba_page_minmax_call(_lib.hx_debug_ba_page_minmax, values,
                                 row_group, skip)
+
+
+BYTES_PAGE_LIMIT_REFERENCE = 1 << 20
+BA_CUT_BATCH = 1024
+
+
+def _ba_batch_sizes_call(fn, row_len, row_group):
+    row_len = np.ascontiguousarray(row_len, dtype=np.uint32)
+    n = len(row_len)
+    n_rg = (n + row_group - 1) // row_group
+    n_b = 0
+    if n_rg:
+        last = n - (n_rg - 1) * row_group
+        n_b = (n_rg - 1) * ((row_group + 1023) // 1024) + (last + 1023) // 1024
+    out = np.full(max(n_b, 1), 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
+    _check(fn(row_len.ctypes.data_as(C.POINTER(C.c_uint32)) if n else None,
+              n, row_group,
+              out.ctypes.data_as(C.POINTER(C.c_uint64)) if n else None))
+    return out[:n_b].copy()
+
+
+def ba_batch_sizes_host(row_len, row_group=8192):
+    """The host twin of kernel 1h (hx_debug_ba_batch_sizes_host; no GPU
+    needed): the byte sum, 4 + len per row and 4 for a BA_ROW_SKIP row, of
+    every 1024-row batch of every row group of row_len (uint32 per row)."""
+    return _ba_batch_sizes_call(_lib.hx_debug_ba_batch_sizes_host, row_len,
+                                row_group)
+
+
+def ba_batch_sizes_device(row_len, row_group=8192):
+    """Kernel 1h through the test hook hx_debug_ba_batch_sizes (needs a GPU):
+    the production launch over device buffers of exactly the stated sizes.
+    Arguments and result as ba_batch_sizes_host."""
+    return _ba_batch_sizes_call(_lib.hx_debug_ba_batch_sizes, row_len,
+                                row_group)
 
 
 def _validity_bits(valid, n):

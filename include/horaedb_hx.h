@@ -353,9 +353,14 @@ hx_status hx_write_sst_codec(const char* path, const uint64_t* series,
  * reference's on-disk form). Read side: value pages may be uncompressed,
  * Snappy or Zstd, data page v1 or v2, the column REQUIRED or OPTIONAL
  * without nulls (the reference declares every column nullable); a null in
- * the value column, and a value chunk of more than one data page, are
- * refused with HX_ERR_UNSUPPORTED. A Snappy value page is decoded on the
- * device into a tail of the staged blob, so value handles keep one base.
+ * the value column is refused with HX_ERR_UNSUPPORTED. A value chunk may
+ * hold any number of data pages (parquet-rs and arrow-cpp close a page once
+ * it reaches 1 MiB); page value counts that do not add up to the chunk's
+ * return HX_ERR_FORMAT. The 8-byte columns keep the one-page contract. A
+ * Snappy value page that is nothing but literals (an incompressible page,
+ * one literal per 64 KiB fragment) is read in place; any other is decoded
+ * on the device into a tail of the staged blob, so value handles keep one
+ * base.
  * THE VALUE LIMIT: a value is at most 2^20 - 1
  * bytes, because the reader describes a value by a handle with 20 length
  * bits (k_ba_offsets refuses a longer one at read time). Every writer
@@ -364,8 +369,10 @@ hx_status hx_write_sst_codec(const char* path, const uint64_t* series,
  * hx_compact_files) whose concatenation of one equal-PK group would exceed
  * it returns HX_ERR_UNSUPPORTED; hx_index_write refuses such a tag key or
  * value (HX_ERR_INVALID). A row group whose value page would exceed
- * INT32_MAX bytes returns HX_ERR_UNSUPPORTED (multi-page chunks are not
- * written). Every refusal comes before anything is written or unlinked.
+ * image would exceed INT32_MAX bytes returns HX_ERR_UNSUPPORTED, with or
+ * without a page limit (hx_set_bytes_page_limit cuts the image into pages,
+ * it does not lift this bound). Every refusal comes before anything is
+ * written or unlinked.
  *
  * hx_compact / hx_compact_files on such a store: Overwrite keeps the
  * winner's bytes (last wins). Append turns each equal-PK run of the inputs,
@@ -425,6 +432,38 @@ hx_status hx_write_sst_bytes_codec(const char* path, const uint64_t* series,
                                    const uint64_t* seqs, uint64_t seq,
                                    int64_t n_rows, int64_t row_group,
                                    int32_t codec);
+
+/* Data-page limit of the Binary writers' value chunks, per handle; default 0
+ * (nothing changes: one data page per chunk, the files byte for byte what
+ * they always were). Otherwise a value in [1, 2^30]: every value chunk that
+ * hx_write_bytes, hx_compact and hx_compact_files write is cut into v1 PLAIN
+ * data pages back to back, by the rule arrow-cpp's writer applies with its
+ * write_batch_size of 1024: rows are taken in batches of 1024 counted from
+ * the row group's first row, a row adds 4 + its length to the open page, and
+ * after a batch a page that has reached the limit closes if rows remain. So
+ * a row group of R rows has at most ceil(R / 1024) pages, none empty, and
+ * the cuts are a pure function of the rows: every route writes the same
+ * file. The pages' bodies concatenated are the one-page image; chunk
+ * statistics are unchanged, and there are no page-level statistics and no
+ * page index. Under HX_CODEC_SNAPPY each page is compressed on its own, one
+ * wave per page on the device routes. A row group that never reaches the
+ * limit is written as under limit 0. HX_BYTES_PAGE_LIMIT_REFERENCE is the
+ * reference writers' data page size. A value above 2^30 returns
+ * HX_ERR_INVALID; a non-zero limit on a store with an f64 value column
+ * returns HX_ERR_UNSUPPORTED. */
+#define HX_BYTES_PAGE_LIMIT_REFERENCE (1u << 20)
+#define HX_BYTES_PAGE_LIMIT_MAX (1u << 30)
+hx_status hx_set_bytes_page_limit(hx_handle*, uint32_t bytes);
+
+/* hx_write_sst_bytes_codec with a page limit (same range, HX_ERR_INVALID
+ * outside it); limit 0 writes the file hx_write_sst_bytes_codec writes, byte
+ * for byte. */
+hx_status hx_write_sst_bytes_paged(const char* path, const uint64_t* series,
+                                   const int64_t* ts, const uint8_t* bytes,
+                                   const int64_t* offsets,
+                                   const uint64_t* seqs, uint64_t seq,
+                                   int64_t n_rows, int64_t row_group,
+                                   int32_t codec, uint32_t page_limit);
 
 /* ---- inverted index (RFC docs/rfcs/20240827-metric-engine.md:86-137) ----
  * The reference's planned index tables (its metric_engine index module is

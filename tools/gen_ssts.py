@@ -196,15 +196,18 @@ def gen_dataset(out_dir, n_rows, n_series, n_ssts, seed=42,
 
 def write_bytes_sst(path, series, ts, values, seq, row_group=8192,
                     sort=True, compression="NONE", nullable=False,
-                    data_page_version="1.0", data_page_size=None):
+                    data_page_version="1.0", data_page_size=None,
+                    write_batch_size=None):
     """One Binary-value SST (BytesMergeOperator stores, operator.rs:47-111):
     (series u64 PK, ts i64 PK, value binary, builtins), PLAIN, writer-sorted
     by (series, ts) stable (equal PKs keep input order). compression: "NONE"
     (default), "SNAPPY" (the reference's default, config.rs:120-133) or
     "ZSTD". nullable: every column is declared OPTIONAL, the reference's
     shape; a value may then be None. data_page_size: pyarrow's page-size
-    limit; the reader takes one data page per chunk, so give one above the
-    largest value page (the default splits a chunk at 1 MiB)."""
+    limit (the default closes a page at 1 MiB). write_batch_size: the rows
+    after which pyarrow looks at the page size (its default is 1024). The
+    8-byte columns must stay one page per chunk; the value chunk may hold
+    several."""
     import pyarrow as pa
     import pyarrow.parquet as pq
     series = np.asarray(series, dtype=np.uint64)
@@ -234,6 +237,8 @@ def write_bytes_sst(path, series, ts, values, seq, row_group=8192,
     os.makedirs(os.path.dirname(path), exist_ok=True)
     extra = {} if data_page_size is None else \
         {"data_page_size": int(data_page_size)}
+    if write_batch_size is not None:
+        extra["write_batch_size"] = int(write_batch_size)
     pq.write_table(tbl, path, row_group_size=row_group,
                    compression=compression, use_dictionary=False,
                    data_page_version=data_page_version,
