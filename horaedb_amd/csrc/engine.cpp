@@ -60,6 +60,13 @@ static hx_status fail(hx_status code, const std::string& msg) {
                                         hipGetErrorString(_e));               \
     } while (0)
 
+// the same inside a function that returns the hipError_t itself
+#define HIP_RET(expr)                                                         \
+    do {                                                                      \
+        hipError_t _e = (expr);                                               \
+        if (_e != hipSuccess) return _e;                                      \
+    } while (0)
+
 // ---------------------------------------------------------------------------
 // catalog (hx_open)
 // ---------------------------------------------------------------------------
@@ -2009,6 +2016,47 @@ extern "C" hx_status hx_get_decode_stats(hx_prepared* P, hx_decode_stats* out) {
     return HX_OK;
 }
 
+namespace {
+
+// device allocations freed at scope exit
+struct DevBufs {
+    std::vector<void*> p;
+    explicit DevBufs(size_t n_slots = 0) : p(n_slots, nullptr) {}
+    ~DevBufs() {
+        for (void* q : p)
+            if (q) (void)hipFree(q);
+    }
+    hipError_t alloc(void** out, size_t bytes) {
+        hipError_t e = hipMalloc(out, bytes ? bytes : 1);
+        if (e == hipSuccess) p.push_back(*out);
+        return e;
+    }
+};
+
+// the radix sort's temporary storage where no plan owns it
+struct SortTemp {
+    void* p = nullptr;
+    size_t cap = 0;
+    ~SortTemp() { if (p) (void)hipFree(p); }
+};
+
+// HX_DEBUG stage timers: N events, created on demand, destroyed at scope exit
+template <int N>
+struct HipEvents {
+    hipEvent_t e[N] = {};
+    ~HipEvents() {
+        for (hipEvent_t v : e)
+            if (v) (void)hipEventDestroy(v);
+    }
+    hipError_t create() {
+        for (hipEvent_t& v : e) HIP_RET(hipEventCreate(&v));
+        return hipSuccess;
+    }
+    hipEvent_t operator[](int i) const { return e[i]; }
+};
+
+}  // namespace
+
 extern "C" hx_status hx_debug_page_levels(
     const char* path, int32_t row_group, const char* column,
     uint64_t* bitmap_out, uint64_t cap_words, int64_t* n_rows,
@@ -2087,13 +2135,7 @@ extern "C" hx_status hx_debug_snappy_decompress(
     for (uint32_t i = 0; i < n; i++)
         std::memcpy(h_blob.data() + pages[i].src_off, streams + offs[i],
                     comp_lens[i]);
-    struct DevBufs {
-        void* p[4] = {nullptr, nullptr, nullptr, nullptr};
-        ~DevBufs() {
-            for (void* q : p)
-                if (q) hipFree(q);
-        }
-    } dev;
+    DevBufs dev(4);
     HIP_TRY(hipMalloc(&dev.p[0], h_blob.size()));
     HIP_TRY(hipMalloc(&dev.p[1], dec_bytes + 64));
     HIP_TRY(hipMalloc(&dev.p[2], size_t(n) * sizeof(hx::SnappyPageDesc)));
@@ -2140,13 +2182,7 @@ extern "C" hx_status hx_debug_pack_optional(
     const size_t valid_bytes =
         valid_words ? size_t(n_src) * 8 : valid_bits ? (size_t(n_src) + 7) / 8
                                                      : 0;
-    struct DevBufs {
-        void* p[7] = {};
-        ~DevBufs() {
-            for (void* q : p)
-                if (q) (void)hipFree(q);
-        }
-    } dev;
+    DevBufs dev(7);
     // every buffer exactly as large as the contract says it is
     HIP_TRY(hipMalloc(&dev.p[0], std::max<size_t>(size_t(n_src) * 8, 8)));
     HIP_TRY(hipMalloc(&dev.p[1], std::max<size_t>(valid_bytes, 8)));
@@ -2217,13 +2253,7 @@ extern "C" hx_status hx_debug_snappy_compress(
         if (lens[i])
             std::memcpy(h_src.data() + descs[i].src_off, pages + offs[i],
                         lens[i]);
-    struct DevBufs {
-        void* p[5] = {};
-        ~DevBufs() {
-            for (void* q : p)
-                if (q) (void)hipFree(q);
-        }
-    } dev;
+    DevBufs dev(5);
     // every buffer exactly as large as the contract says it is
     HIP_TRY(hipMalloc(&dev.p[0], std::max<size_t>(src_bytes, 1)));
     HIP_TRY(hipMalloc(&dev.p[1], std::max<size_t>(out_bytes, 1)));
@@ -2266,6 +2296,150 @@ extern "C" hx_status hx_scan_agg(hx_handle* h, const hx_scan_spec* spec,
     return st;
 }
 
+namespace {
+
+// The (series, ts) sort permutation of the ingest sort and of every row
+// stream: stable, equal PKs keep the order they come in. Two stable LSD radix
+// passes over a u32 permutation, ts (sign-biased) then series; pc receives
+// the result, d_ka / d_kb / pb are N-entry scratch. pa is the order the rows
+// come in: iota, written here, unless pa_given (the Append pass of
+// sorted_row_stream has already ordered it by sequence).
+hipError_t ingest_sort_perm(hipStream_t s, const uint64_t* d_series,
+                            const int64_t* d_ts, uint64_t* d_ka,
+                            uint64_t* d_kb, uint32_t* pa, uint32_t* pb,
+                            uint32_t* pc, size_t N, void** d_temp,
+                            size_t* temp_cap, bool pa_given = false) {
+    if (!pa_given) HIP_RET(hx::launch_iota(s, pa, (uint32_t)N));
+    HIP_RET(hx::launch_gather_u64(s, (const unsigned long long*)d_ts, pa,
+                                  (unsigned long long*)d_ka, (uint32_t)N));
+    HIP_RET(hx::launch_xor_sign(s, (unsigned long long*)d_ka, (uint32_t)N));
+    HIP_RET(hx::sort_pairs_u64(s, d_ka, d_kb, pa, pb, N, d_temp, temp_cap));
+    HIP_RET(hx::launch_gather_u64(s, (const unsigned long long*)d_series, pb,
+                                  (unsigned long long*)d_ka, (uint32_t)N));
+    HIP_RET(hx::sort_pairs_u64(s, d_ka, d_kb, pb, pc, N, d_temp, temp_cap));
+    return hipSuccess;
+}
+
+using PreparedPtr = std::unique_ptr<hx_prepared, void (*)(hx_prepared*)>;
+
+// hx_prepare on the first device given (device 0 without one): the row
+// stream routes are single-device
+hx_status prepare_single(hx_handle* h, const hx_scan_spec* spec,
+                         const hx_device_set* devs, PreparedPtr& out) {
+    int32_t dev0 = (devs && devs->device_ids && devs->n_devices > 0)
+                       ? devs->device_ids[0] : 0;
+    hx_device_set one{&dev0, 1};
+    hx_prepared* P = nullptr;
+    hx_status st = hx_prepare(h, spec, &one, &P);
+    out.reset(P);
+    return st;
+}
+
+// The filtered row stream of a prepared plan, in (series, ts) order: what
+// hx_scan, compact_rows and compact_rows_bytes start from. Views into
+// plan.d_scratch, valid until the plan's scratch is used again.
+struct RowStream {
+    uint64_t* series = nullptr;
+    long long* ts = nullptr;
+    double* val = nullptr;        // f64 values, or Binary value handles
+    uint64_t* seq = nullptr;      // null unless asked for (or Append)
+    uint64_t* valid = nullptr;    // one 0/1 word per row; null unless the
+                                  // plan staged a null
+    uint64_t* keys = nullptr;     // two n-word buffers, free for the caller
+    uint64_t* keys_out = nullptr; // after the sort
+    uint32_t* perm = nullptr;     // rows in (series, ts) order
+    uint32_t* spare_a = nullptr;  // two more n-entry permutations
+    uint32_t* spare_b = nullptr;
+    uint32_t n = 0;               // surviving rows; 0: no view is to be used
+};
+
+// Scan (filter, and last-wins dedup unless Append), count, sort. Append
+// (UpdateMode config.rs:166-172 -> BytesMergeOperator, operator.rs:47-111)
+// keeps every row, and a leading stable pass on the packed (seq << 32 | file
+// row) key leaves equal-PK rows in ascending __seq__ order, the operator's
+// concat order (MergeStream group order, read.rs:289-343). `what` names the
+// caller in the overflow message.
+hx_status sorted_row_stream(hx_handle* h, hx_prepared* P, DevPlan& plan,
+                            bool want_seq, bool append, const char* what,
+                            RowStream& out) {
+    out = RowStream{};
+    HIP_TRY(hipSetDevice(plan.device));
+    hipStream_t s = plan.stream;
+    hx_status st = ensure_decoded(plan, s);
+    if (st != HX_OK) return st;
+    st = ensure_sset(P, plan);
+    if (st != HX_OK) return st;
+    const uint64_t cap = (uint64_t)plan.rows_scanned;
+    if (cap == 0) return HX_OK;
+    if (cap > 0xFFFFFFFFull)
+        return fail(HX_ERR_UNSUPPORTED,
+                    "row streams above 2^32 rows per call: split the range");
+    if (append)   // the packed sort key has 32 bits for the sequence
+        for (const auto& c : h->ssts)
+            if (c.seq >= (1ull << 32))
+                return fail(HX_ERR_UNSUPPORTED,
+                            "append stores need file sequences < 2^32");
+    want_seq = want_seq || append;
+    const bool nulls = plan.has_nulls;   // never with Append / Binary values
+    // 8-byte buffers first (3 columns, 2 key buffers [, seq] [, valid], the
+    // cursor), the three permutations last
+    const size_t need =
+        cap * 8 * (5 + (want_seq ? 1 : 0) + (nulls ? 1 : 0)) + cap * 4 * 3 + 64;
+    st = ensure_dev(&plan.d_scratch, &plan.scratch_cap, need);
+    if (st != HX_OK) return st;
+    uint64_t* w = (uint64_t*)plan.d_scratch;
+    auto carve8 = [&](size_t count) {
+        uint64_t* p = w;
+        w += count;
+        return p;
+    };
+    out.series = carve8(cap);
+    out.ts = (long long*)carve8(cap);
+    out.val = (double*)carve8(cap);
+    if (want_seq) out.seq = carve8(cap);
+    if (nulls) out.valid = carve8(cap);
+    out.keys = carve8(cap);
+    out.keys_out = carve8(cap);
+    unsigned long long* d_cursor = (unsigned long long*)carve8(1);
+    uint32_t* pa = (uint32_t*)w;
+    uint32_t* pb = pa + cap;
+    uint32_t* pc = pb + cap;
+
+    HIP_TRY(hipMemsetAsync(d_cursor, 0, 8, s));
+    hx::AggParams A = base_params(P, plan);
+    if (append) A.keep_dups = 1;   // keep every row: groups concatenate
+    HIP_TRY(hx::launch_scan_rows(s, A, 0, A.n_rgs, out.series, out.ts,
+                                 out.val, d_cursor, cap, out.seq,
+                                 append ? 1 : 0, out.valid));
+    unsigned long long n64 = 0;
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpy(&n64, d_cursor, 8, hipMemcpyDeviceToHost));
+    if (n64 > cap)
+        return fail(HX_ERR_HIP, std::string(what) + " row buffer overflow");
+    const uint32_t n = (uint32_t)n64;
+    if (n == 0) return HX_OK;
+
+    // LSD-stable ordering: [seq,] ts, then series
+    if (append) {
+        HIP_TRY(hx::launch_iota(s, pa, n));
+        HIP_TRY(hx::launch_gather_u64(s, (const unsigned long long*)out.seq,
+                                      pa, (unsigned long long*)out.keys, n));
+        HIP_TRY(hx::sort_pairs_u64(s, out.keys, out.keys_out, pa, pb, n,
+                                   &plan.d_sort_temp, &plan.sort_temp_cap));
+        std::swap(pa, pb);
+    }
+    HIP_TRY(ingest_sort_perm(s, out.series, (const int64_t*)out.ts, out.keys,
+                             out.keys_out, pa, pb, pc, n, &plan.d_sort_temp,
+                             &plan.sort_temp_cap, append));
+    out.perm = pc;
+    out.spare_a = pa;
+    out.spare_b = pb;
+    out.n = n;
+    return HX_OK;
+}
+
+}  // namespace
+
 extern "C" hx_status hx_scan(hx_handle* h, const hx_scan_spec* spec,
                              const hx_device_set* devs, hx_batch_cb cb,
                              void* ctx) {
@@ -2277,120 +2451,44 @@ extern "C" hx_status hx_scan(hx_handle* h, const hx_scan_spec* spec,
     // device.
     if (!h || !spec || !cb) return fail(HX_ERR_INVALID, "null argument");
     const bool bytesv = h->bytes_value;
-    // Append mode (UpdateMode config.rs:166-172 -> BytesMergeOperator,
-    // operator.rs:47-111): every filtered row is kept (no last-wins dedup)
-    // and equal-PK groups concatenate their value bytes in ascending
-    // __seq__ order (MergeStream group order, read.rs:289-343).
+    // Append mode: equal-PK groups concatenate their value bytes in the
+    // order sorted_row_stream leaves them in
     const bool append = h->update_mode == 1;
     if (append && !bytesv)
         return fail(HX_ERR_UNSUPPORTED,
                     "Append mode needs a Binary value column");
-    int32_t dev0 = (devs && devs->device_ids && devs->n_devices > 0)
-                       ? devs->device_ids[0] : 0;
-    hx_device_set one{&dev0, 1};
-    hx_prepared* P = nullptr;
-    hx_status st = hx_prepare(h, spec, &one, &P);
+    PreparedPtr P(nullptr, hx_prepared_free);
+    hx_status st = prepare_single(h, spec, devs, P);
     if (st != HX_OK) return st;
-    std::unique_ptr<hx_prepared, void (*)(hx_prepared*)> guard(
-        P, hx_prepared_free);
     DevPlan& plan = P->plans[0];
-    HIP_TRY(hipSetDevice(plan.device));
-    hipStream_t s = plan.stream;
-    st = ensure_decoded(plan, s);
+    RowStream rs;
+    st = sorted_row_stream(h, P.get(), plan, false, append, "scan", rs);
     if (st != HX_OK) return st;
-    st = ensure_sset(P, plan);
-    if (st != HX_OK) return st;
-
-    const uint64_t cap = (uint64_t)plan.rows_scanned;
-    if (cap == 0) return HX_OK;
-    if (cap > 0xFFFFFFFFull)
-        return fail(HX_ERR_UNSUPPORTED,
-                    "row streams above 2^32 rows per call: split the range");
-    // device buffers: 3-4 columns + sort keys/scratch + 3 perms
-    const bool nulls = plan.has_nulls;   // never with append / Binary values
-    size_t need = cap * 8 * ((append ? 6 : 5) + (nulls ? 1 : 0)) +
-                  cap * 4 * 3 + 64;
-    st = ensure_dev(&plan.d_scratch, &plan.scratch_cap, need);
-    if (st != HX_OK) return st;
-    uint8_t* base = (uint8_t*)plan.d_scratch;
-    auto carve8 = [&](size_t count) {
-        uint8_t* p = base;
-        base += (count * 8 + 7) & ~size_t(7);
-        return p;
-    };
-    uint64_t* d_series = (uint64_t*)carve8(cap);
-    long long* d_ts = (long long*)carve8(cap);
-    double* d_val = (double*)carve8(cap);
-    uint64_t* d_seq = append ? (uint64_t*)carve8(cap) : nullptr;
-    // one 0/1 word per surviving row: rides the same permutation as value
-    uint64_t* d_valid = nulls ? (uint64_t*)carve8(cap) : nullptr;
-    uint64_t* d_keys = (uint64_t*)carve8(cap);
-    uint64_t* d_keys_out = (uint64_t*)carve8(cap);
-    unsigned long long* d_cursor = (unsigned long long*)carve8(1);
-    uint32_t* perm_a = (uint32_t*)base; base += cap * 4;
-    uint32_t* perm_b = (uint32_t*)base; base += cap * 4;
-    uint32_t* perm_c = (uint32_t*)base; base += cap * 4;
-
-    HIP_TRY(hipMemsetAsync(d_cursor, 0, 8, s));
-    hx::AggParams A = base_params(P, plan);
-    if (append) {
-        A.keep_dups = 1;   // keep every row: groups concatenate
-        // the packed (seq << 32 | row) sort key needs seq < 2^32
-        for (const auto& c : h->ssts)
-            if (c.seq >= (1ull << 32))
-                return fail(HX_ERR_UNSUPPORTED,
-                            "append stores need file sequences < 2^32");
-    }
-    HIP_TRY(hx::launch_scan_rows(s, A, 0, A.n_rgs, d_series, d_ts, d_val,
-                                 d_cursor, cap, d_seq, append ? 1 : 0,
-                                 d_valid));
-    unsigned long long n64 = 0;
-    HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(hipMemcpy(&n64, d_cursor, 8, hipMemcpyDeviceToHost));
-    if (n64 > cap)
-        return fail(HX_ERR_HIP, "scan row buffer overflow");
-    const uint32_t n = (uint32_t)n64;
+    const uint32_t n = rs.n;
     if (n == 0) return HX_OK;
-
-    // LSD-stable ordering: [seq,] ts, then series, then time segment
-    HIP_TRY(hx::launch_iota(s, perm_a, n));
-    if (append) {
-        // least-significant pass first: group rows end up in ascending
-        // __seq__ order (the BytesMergeOperator concat order)
-        HIP_TRY(hx::launch_gather_u64(s, (const unsigned long long*)d_seq,
-                                      perm_a, (unsigned long long*)d_keys,
-                                      n));
-        HIP_TRY(hx::sort_pairs_u64(s, d_keys, d_keys_out, perm_a, perm_b, n,
-                                   &plan.d_sort_temp, &plan.sort_temp_cap));
-        std::swap(perm_a, perm_b);
-    }
-    HIP_TRY(hx::launch_gather_u64(s, (const unsigned long long*)d_ts, perm_a,
-                                  (unsigned long long*)d_keys, n));
-    HIP_TRY(hx::launch_xor_sign(s, (unsigned long long*)d_keys, n));
-    HIP_TRY(hx::sort_pairs_u64(s, d_keys, d_keys_out, perm_a, perm_b, n,
-                               &plan.d_sort_temp, &plan.sort_temp_cap));
-    HIP_TRY(hx::launch_gather_u64(s, (const unsigned long long*)d_series,
-                                  perm_b, (unsigned long long*)d_keys, n));
-    HIP_TRY(hx::sort_pairs_u64(s, d_keys, d_keys_out, perm_b, perm_c, n,
-                               &plan.d_sort_temp, &plan.sort_temp_cap));
-    // segment keys from the (permuted) ts values
-    HIP_TRY(hx::launch_gather_u64(s, (const unsigned long long*)d_ts, perm_c,
-                                  (unsigned long long*)d_keys_out, n));
-    HIP_TRY(hx::launch_seg_keys(s, (const long long*)d_keys_out, h->segment_ms,
-                                (unsigned long long*)d_keys, n));
-    HIP_TRY(hx::sort_pairs_u64(s, d_keys, d_keys_out, perm_c, perm_a, n,
-                               &plan.d_sort_temp, &plan.sort_temp_cap));
-    const uint32_t* perm = perm_a;
+    hipStream_t s = plan.stream;
+    const bool nulls = rs.valid != nullptr;
+    // fourth pass, most significant: the time segment of the (permuted) ts
+    HIP_TRY(hx::launch_gather_u64(s, (const unsigned long long*)rs.ts,
+                                  rs.perm, (unsigned long long*)rs.keys_out,
+                                  n));
+    HIP_TRY(hx::launch_seg_keys(s, (const long long*)rs.keys_out,
+                                h->segment_ms, (unsigned long long*)rs.keys,
+                                n));
+    HIP_TRY(hx::sort_pairs_u64(s, rs.keys, rs.keys_out, rs.perm, rs.spare_a,
+                               n, &plan.d_sort_temp, &plan.sort_temp_cap));
+    const uint32_t* perm = rs.spare_a;
 
     // gather the three columns by the final permutation, one D2H
     const unsigned long long* srcs[4] = {
-        (const unsigned long long*)d_series, (const unsigned long long*)d_ts,
-        (const unsigned long long*)d_val, (const unsigned long long*)d_valid};
+        (const unsigned long long*)rs.series, (const unsigned long long*)rs.ts,
+        (const unsigned long long*)rs.val, (const unsigned long long*)rs.valid};
     const uint32_t n_src = nulls ? 4 : 3;
     // reuse keys buffers as gather dst (need 3n; keys has 2n) — allocate
     std::vector<uint64_t> host(n_src * size_t(n));
+    DevBufs dev;
     unsigned long long* d_dst = nullptr;
-    HIP_TRY(hipMalloc((void**)&d_dst, n_src * size_t(n) * 8));
+    HIP_TRY(dev.alloc((void**)&d_dst, n_src * size_t(n) * 8));
     HIP_TRY(hx::launch_gather_multi(s, srcs, n_src, perm, d_dst, n));
     HIP_TRY(hipMemcpyAsync(host.data(), d_dst, n_src * size_t(n) * 8,
                            hipMemcpyDeviceToHost, s));
@@ -2434,8 +2532,8 @@ extern "C" hx_status hx_scan(hx_handle* h, const hx_scan_spec* spec,
         const int64_t total = row_off[n];
         int64_t* d_offs = nullptr;
         uint8_t* d_bytes = nullptr;
-        HIP_TRY(hipMalloc((void**)&d_offs, (size_t(n) + 1) * 8));
-        HIP_TRY(hipMalloc((void**)&d_bytes, size_t(std::max<int64_t>(
+        HIP_TRY(dev.alloc((void**)&d_offs, (size_t(n) + 1) * 8));
+        HIP_TRY(dev.alloc((void**)&d_bytes, size_t(std::max<int64_t>(
                                                 total, 1))));
         HIP_TRY(hipMemcpyAsync(d_offs, row_off.data(), (size_t(n) + 1) * 8,
                                hipMemcpyHostToDevice, s));
@@ -2447,13 +2545,10 @@ extern "C" hx_status hx_scan(hx_handle* h, const hx_scan_spec* spec,
             HIP_TRY(hipMemcpyAsync(hbytes.data(), d_bytes, size_t(total),
                                    hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        (void)hipFree(d_offs);
-        (void)hipFree(d_bytes);
         if (!append) {
             group_off = std::move(row_off);
         }
     }
-    (void)hipFree(d_dst);
 
     // projection over user columns (storage.rs:65-70; builtins stripped as
     // MergeStream does, read.rs:330-343)
@@ -2547,6 +2642,14 @@ struct PackedValues {
     hx::NullableValues view() const {
         return {packed.data(), bitmap.data(), n_valid.data()};
     }
+    // kernel 1d's host twin over n rows; order: the sort permutation or null
+    void pack_host(const double* value, const uint8_t* validity,
+                   const uint32_t* order, int64_t n, int64_t row_group) {
+        resize(n, row_group);
+        hx::pack_optional_host((const uint64_t*)value, validity, order,
+                               (uint64_t)n, (uint64_t)n, (uint64_t)row_group,
+                               packed.data(), bitmap.data(), n_valid.data());
+    }
 };
 
 // Snappy streams of a file's pages, made on the device (kernel 1e) and
@@ -2612,12 +2715,10 @@ hipError_t compress_columns_device(hipStream_t s, const uint8_t* d_base,
     const size_t back_words =
         err_word + 1 + size_t(n_pages) * (sizeof(hx::PageStat) / 8);
     uint8_t* dev = nullptr;
-    hipError_t e = hipMalloc((void**)&dev, 2 * slot_bytes + desc_bytes +
-                                               kind_bytes + off_bytes +
-                                               back_words * 8);
-    if (e != hipSuccess) return e;
-    std::unique_ptr<void, void (*)(void*)> guard(
-        dev, [](void* q) { (void)hipFree(q); });
+    DevBufs bufs;
+    HIP_RET(bufs.alloc((void**)&dev, 2 * slot_bytes + desc_bytes +
+                                         kind_bytes + off_bytes +
+                                         back_words * 8));
     uint8_t* d_slots = dev;
     uint8_t* d_packed = dev + slot_bytes;
     auto* d_descs = (hx::SnappyCompDesc*)(d_packed + slot_bytes);
@@ -2626,33 +2727,31 @@ hipError_t compress_columns_device(hipStream_t s, const uint8_t* d_base,
     uint32_t* d_lens = (uint32_t*)((uint8_t*)d_offs + off_bytes);
     unsigned long long* d_err = (unsigned long long*)d_lens + err_word;
     hx::PageStat* d_stats = (hx::PageStat*)(d_err + 1);
-#define CS_TRY(x) do { e = (x); if (e != hipSuccess) return e; } while (0)
-    CS_TRY(hipMemcpyAsync(d_descs, descs.data(),
-                          size_t(n_pages) * sizeof(descs[0]),
-                          hipMemcpyHostToDevice, s));
-    CS_TRY(hipMemcpyAsync(d_kinds, kinds.data(), size_t(n_pages) * 4,
-                          hipMemcpyHostToDevice, s));
-    CS_TRY(hipMemsetAsync(d_err, 0, 8, s));
-    CS_TRY(hx::launch_snappy_compress(s, d_base, d_slots, d_descs, n_pages,
-                                      d_lens, d_err));
-    CS_TRY(hx::launch_page_minmax(s, d_base, d_descs, d_kinds, n_pages,
-                                  d_stats));
-    CS_TRY(hx::launch_snappy_pack(s, d_slots, d_descs, n_pages, d_lens,
-                                  d_offs, d_packed));
-    if (after_pack) CS_TRY(hipEventRecord(after_pack, s));
+    HIP_RET(hipMemcpyAsync(d_descs, descs.data(),
+                           size_t(n_pages) * sizeof(descs[0]),
+                           hipMemcpyHostToDevice, s));
+    HIP_RET(hipMemcpyAsync(d_kinds, kinds.data(), size_t(n_pages) * 4,
+                           hipMemcpyHostToDevice, s));
+    HIP_RET(hipMemsetAsync(d_err, 0, 8, s));
+    HIP_RET(hx::launch_snappy_compress(s, d_base, d_slots, d_descs, n_pages,
+                                       d_lens, d_err));
+    HIP_RET(hx::launch_page_minmax(s, d_base, d_descs, d_kinds, n_pages,
+                                   d_stats));
+    HIP_RET(hx::launch_snappy_pack(s, d_slots, d_descs, n_pages, d_lens,
+                                   d_offs, d_packed));
+    if (after_pack) HIP_RET(hipEventRecord(after_pack, s));
     std::vector<uint64_t> lens_host(back_words);
-    CS_TRY(hipMemcpyAsync(lens_host.data(), d_lens, lens_host.size() * 8,
-                          hipMemcpyDeviceToHost, s));
-    CS_TRY(hipStreamSynchronize(s));
+    HIP_RET(hipMemcpyAsync(lens_host.data(), d_lens, lens_host.size() * 8,
+                           hipMemcpyDeviceToHost, s));
+    HIP_RET(hipStreamSynchronize(s));
     if (lens_host[err_word] != 0) return hipErrorUnknown;
     const uint32_t* lens = (const uint32_t*)lens_host.data();
     size_t total = 0;
     for (uint32_t i = 0; i < n_pages; i++) total += lens[i];
     out.bytes.resize(total);
-    CS_TRY(hipMemcpyAsync(out.bytes.data(), d_packed, total,
-                          hipMemcpyDeviceToHost, s));
-    CS_TRY(hipStreamSynchronize(s));
-#undef CS_TRY
+    HIP_RET(hipMemcpyAsync(out.bytes.data(), d_packed, total,
+                           hipMemcpyDeviceToHost, s));
+    HIP_RET(hipStreamSynchronize(s));
     const hx::PageStat* stats =
         (const hx::PageStat*)(lens_host.data() + err_word + 1);
     size_t at = 0;
@@ -2682,20 +2781,8 @@ extern "C" hx_status hx_write_sst_nullable(
     const char* path, const uint64_t* series, const int64_t* ts,
     const double* value, const uint8_t* validity, uint64_t seq,
     int64_t n_rows, int64_t row_group) {
-    if (!path || !series || !ts || !value || n_rows <= 0 || row_group <= 0)
-        return fail(HX_ERR_INVALID, "bad argument");
-    if (row_group % 64)
-        return fail(HX_ERR_INVALID, "row_group is not a multiple of 64");
-    PackedValues pv;
-    pv.resize(n_rows, row_group);
-    hx::pack_optional_host((const uint64_t*)value, validity, nullptr,
-                           (uint64_t)n_rows, (uint64_t)n_rows,
-                           (uint64_t)row_group, pv.packed.data(),
-                           pv.bitmap.data(), pv.n_valid.data());
-    std::string err = hx::write_metric_sst_nullable(
-        path, series, ts, pv.view(), nullptr, seq, n_rows, row_group);
-    if (!err.empty()) return fail(HX_ERR_IO, err);
-    return HX_OK;
+    return hx_write_sst_codec(path, series, ts, value, validity, 1, seq,
+                              n_rows, row_group, HX_CODEC_NONE);
 }
 
 extern "C" hx_status hx_write_sst_codec(
@@ -2719,11 +2806,7 @@ extern "C" hx_status hx_write_sst_codec(
         if (row_group % 64)
             return fail(HX_ERR_INVALID, "row_group is not a multiple of 64");
         PackedValues pv;
-        pv.resize(n_rows, row_group);
-        hx::pack_optional_host((const uint64_t*)value, validity, nullptr,
-                               (uint64_t)n_rows, (uint64_t)n_rows,
-                               (uint64_t)row_group, pv.packed.data(),
-                               pv.bitmap.data(), pv.n_valid.data());
+        pv.pack_host(value, validity, nullptr, n_rows, row_group);
         err = hx::write_metric_sst_nullable(path, series, ts, pv.view(),
                                             nullptr, seq, n_rows, row_group,
                                             codec);
@@ -2738,48 +2821,104 @@ extern "C" uint64_t hx_debug_snappy_compress_host(const uint8_t* src,
     return hx::snappy_compress_host(src, size_t(n), dst, size_t(cap));
 }
 
-// The ingest sort's permutation, shared by hx_write and hx_write_bytes:
-// stable by (series, ts), equal PKs keep input order. Two stable LSD radix
-// passes over a u32 permutation, ts (sign-biased) then series; pc receives
-// the result, d_ka / d_kb / pa / pb are N-entry scratch.
-static hipError_t ingest_sort_perm(hipStream_t s, const uint64_t* d_series,
-                                   const int64_t* d_ts, uint64_t* d_ka,
-                                   uint64_t* d_kb, uint32_t* pa, uint32_t* pb,
-                                   uint32_t* pc, size_t N, void** d_temp,
-                                   size_t* temp_cap) {
-#define SP_TRY(e) do { hipError_t e_ = (e); if (e_ != hipSuccess) return e_; } while (0)
-    SP_TRY(hx::launch_iota(s, pa, (uint32_t)N));
-    SP_TRY(hx::launch_gather_u64(s, (const unsigned long long*)d_ts, pa,
-                                 (unsigned long long*)d_ka, (uint32_t)N));
-    SP_TRY(hx::launch_xor_sign(s, (unsigned long long*)d_ka, (uint32_t)N));
-    SP_TRY(hx::sort_pairs_u64(s, d_ka, d_kb, pa, pb, N, d_temp, temp_cap));
-    SP_TRY(hx::launch_gather_u64(s, (const unsigned long long*)d_series, pb,
-                                 (unsigned long long*)d_ka, (uint32_t)N));
-    SP_TRY(hx::sort_pairs_u64(s, d_ka, d_kb, pb, pc, N, d_temp, temp_cap));
-#undef SP_TRY
-    return hipSuccess;
+// ---------------------------------------------------------------------------
+// what hx_write, hx_write_bytes and the compactions share around their routes
+// ---------------------------------------------------------------------------
+
+// Segment-crossing check of a write (storage.rs:309-316). The reference uses
+// Rust truncating division on start/seg vs (end-1)/seg, where end is the
+// exclusive max; C++ `/` truncates the same way, so negative-timestamp writes
+// agree with the reference.
+static hx_status check_segment(const hx_handle* h, const int64_t* ts,
+                               int64_t n) {
+    const auto mm = std::minmax_element(ts, ts + n);
+    if (*mm.first / h->segment_ms != *mm.second / h->segment_ms)
+        return fail(HX_ERR_INVALID,
+                    "write crosses a segment boundary (storage.rs:309-316)");
+    return HX_OK;
+}
+
+// The host route's ingest sort: the stable (series, ts) order, equal PKs keep
+// batch order (LastValueOperator's last-wins, operator.rs:37-44, and the
+// scan's Append key (seq << 32 | file row) depend on it).
+static std::vector<uint32_t> host_pk_order(const uint64_t* series,
+                                           const int64_t* ts, int64_t n) {
+    std::vector<uint32_t> order(n);
+    for (int64_t i = 0; i < n; i++) order[i] = (uint32_t)i;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+        if (series[a] != series[b]) return series[a] < series[b];
+        return ts[a] < ts[b];
+    });
+    return order;
+}
+
+// A fresh file: its id (= sequence, one above the catalog's highest,
+// sst.rs:39-46) and its path.
+struct NewSst {
+    uint64_t seq;
+    std::string path;
+};
+
+static NewSst next_sst(const hx_handle* h) {
+    uint64_t max_seq = 0;
+    for (const auto& s : h->ssts) max_seq = std::max(max_seq, s.seq);
+    return {max_seq + 1,
+            h->store + "/data/" + std::to_string(max_seq + 1) + ".sst"};
+}
+
+// manifest add_file (manifest/mod.rs:115-157): the written file, read back
+static hx_status catalog_add(hx_handle* h, const NewSst& f) {
+    CatSst fresh;
+    hx_status st = read_file_meta(f.path, f.seq, fresh);
+    if (st != HX_OK) return st;
+    h->ssts.push_back(std::move(fresh));
+    return HX_OK;
+}
+
+// A compaction's catalog update: add the new file, drop + unlink the inputs
+// (add-before-delete, executor.rs:206-220).
+static hx_status finish_compaction(hx_handle* h, const NewSst& f,
+                                   const std::vector<char>& in_set,
+                                   uint64_t* out_new_seq) {
+    CatSst fresh;
+    hx_status st = read_file_meta(f.path, f.seq, fresh);
+    if (st != HX_OK) return st;
+    std::vector<CatSst> kept;
+    for (size_t i = 0; i < h->ssts.size(); i++) {
+        if (in_set[i]) {
+            unlink(h->ssts[i].path.c_str());  // best-effort, like the reference
+            continue;
+        }
+        kept.push_back(std::move(h->ssts[i]));
+    }
+    kept.push_back(std::move(fresh));
+    std::sort(kept.begin(), kept.end(),
+              [](const CatSst& a, const CatSst& b) { return a.seq < b.seq; });
+    h->ssts = std::move(kept);
+    *out_new_seq = f.seq;
+    return HX_OK;
 }
 
 // GPU ingest sort (stable by (series, ts); equal PKs keep input order):
-// two stable LSD radix passes over a u32 permutation — ts (sign-biased),
-// then series — then a device gather and one D2H. Returns false on any HIP
-// error so the caller falls back to the host sort. With `pv` (nullable
-// writer) the validity bitmap is uploaded as it is, n / 8 bytes, the gather
-// takes series and ts only, and kernel 1d packs the values by the same
-// permutation; v2 is not written. With `streams` (write codec Snappy) kernel
-// 1e compresses the sorted columns where the gather left them — series, ts
-// and, in the REQUIRED form, value — and their streams come back too.
-static bool gpu_sort_batch(const uint64_t* series, const int64_t* ts,
-                           const double* value, int64_t n,
-                           std::vector<uint64_t>& s2, std::vector<int64_t>& t2,
-                           std::vector<double>& v2,
-                           const uint8_t* validity = nullptr,
-                           PackedValues* pv = nullptr,
-                           DeviceStreams* streams = nullptr) {
+// ingest_sort_perm, then a device gather and one D2H. Any HIP error is
+// returned, not reported: the caller falls back to the host sort. With `pv`
+// (nullable writer) the validity bitmap is uploaded as it is, n / 8 bytes,
+// the gather takes series and ts only, and kernel 1d packs the values by the
+// same permutation; v2 is not written. With `streams` (write codec Snappy)
+// kernel 1e compresses the sorted columns where the gather left them (series,
+// ts and, in the REQUIRED form, value) and their streams come back too.
+static hipError_t gpu_sort_batch(const uint64_t* series, const int64_t* ts,
+                                 const double* value, int64_t n,
+                                 std::vector<uint64_t>& s2,
+                                 std::vector<int64_t>& t2,
+                                 std::vector<double>& v2,
+                                 const uint8_t* validity = nullptr,
+                                 PackedValues* pv = nullptr,
+                                 DeviceStreams* streams = nullptr) {
     hipStream_t s = nullptr;
     uint8_t* dev = nullptr;
-    void* d_temp = nullptr;
-    size_t temp_cap = 0;
+    DevBufs bufs;
+    SortTemp temp;
     const size_t N = (size_t)n;
     const size_t n_groups = (N + kRowGroup - 1) / kRowGroup;
     const size_t bm_words = n_groups * (kRowGroup / 64);
@@ -2787,13 +2926,7 @@ static bool gpu_sort_batch(const uint64_t* series, const int64_t* ts,
     // [, validity bitmap, output bitmaps, n_valid, error count]
     size_t bytes = N * 8 * 8 + N * 4 * 3 + 256;
     if (pv) bytes += (N + 7) / 8 + 8 + bm_words * 8 + n_groups * 4 + 8 + 16;
-    bool ok = hipMalloc((void**)&dev, bytes) == hipSuccess;
-    auto fail_out = [&]() {
-        if (d_temp) (void)hipFree(d_temp);
-        if (dev) (void)hipFree(dev);
-        return false;
-    };
-    if (!ok) return fail_out();
+    HIP_RET(bufs.alloc((void**)&dev, bytes));
     uint8_t* p = dev;
     auto carve = [&](size_t cnt, size_t w) {
         uint8_t* q = p;
@@ -2809,12 +2942,11 @@ static bool gpu_sort_batch(const uint64_t* series, const int64_t* ts,
     uint32_t* pa = (uint32_t*)carve(N, 4);
     uint32_t* pb = (uint32_t*)carve(N, 4);
     uint32_t* pc = (uint32_t*)carve(N, 4);
-#define GS_TRY(e) do { if ((e) != hipSuccess) return fail_out(); } while (0)
-    GS_TRY(hipMemcpyAsync(d_series, series, N * 8, hipMemcpyHostToDevice, s));
-    GS_TRY(hipMemcpyAsync(d_ts, ts, N * 8, hipMemcpyHostToDevice, s));
-    GS_TRY(hipMemcpyAsync(d_val, value, N * 8, hipMemcpyHostToDevice, s));
-    GS_TRY(ingest_sort_perm(s, d_series, d_ts, d_ka, d_kb, pa, pb, pc, N,
-                            &d_temp, &temp_cap));
+    HIP_RET(hipMemcpyAsync(d_series, series, N * 8, hipMemcpyHostToDevice, s));
+    HIP_RET(hipMemcpyAsync(d_ts, ts, N * 8, hipMemcpyHostToDevice, s));
+    HIP_RET(hipMemcpyAsync(d_val, value, N * 8, hipMemcpyHostToDevice, s));
+    HIP_RET(ingest_sort_perm(s, d_series, d_ts, d_ka, d_kb, pa, pb, pc, N,
+                             &temp.p, &temp.cap));
     const unsigned long long* srcs[3] = {
         (const unsigned long long*)d_series, (const unsigned long long*)d_ts,
         (const unsigned long long*)d_val};
@@ -2825,11 +2957,11 @@ static bool gpu_sort_batch(const uint64_t* series, const int64_t* ts,
         uint32_t* d_nv = (uint32_t*)carve(n_groups, 4);
         unsigned long long* d_err = (unsigned long long*)carve(1, 8);
         if (validity)
-            GS_TRY(hipMemcpyAsync(d_vbits, validity, (N + 7) / 8,
-                                  hipMemcpyHostToDevice, s));
-        GS_TRY(hipMemsetAsync(d_err, 0, 8, s));
-        GS_TRY(hx::launch_gather_multi(s, srcs, 2, pc, d_dst, (uint32_t)N));
-        GS_TRY(hx::launch_pack_optional(
+            HIP_RET(hipMemcpyAsync(d_vbits, validity, (N + 7) / 8,
+                                   hipMemcpyHostToDevice, s));
+        HIP_RET(hipMemsetAsync(d_err, 0, 8, s));
+        HIP_RET(hx::launch_gather_multi(s, srcs, 2, pc, d_dst, (uint32_t)N));
+        HIP_RET(hx::launch_pack_optional(
             s, (const unsigned long long*)d_val, validity ? d_vbits : nullptr,
             true, pc, (uint32_t)N, (uint32_t)N, (uint32_t)kRowGroup,
             d_dst + 2 * N, d_bm, d_nv, d_err));
@@ -2837,22 +2969,22 @@ static bool gpu_sort_batch(const uint64_t* series, const int64_t* ts,
         unsigned long long errs = 0;
         // with streams only the packed values come back, series and ts stay
         const size_t from = streams ? 2 * N : 0;
-        GS_TRY(hipMemcpyAsync(host.data() + from, d_dst + from,
-                              (3 * N - from) * 8, hipMemcpyDeviceToHost, s));
-        GS_TRY(hipMemcpyAsync(pv->bitmap.data(), d_bm, bm_words * 8,
-                              hipMemcpyDeviceToHost, s));
-        GS_TRY(hipMemcpyAsync(pv->n_valid.data(), d_nv, n_groups * 4,
-                              hipMemcpyDeviceToHost, s));
-        GS_TRY(hipMemcpyAsync(&errs, d_err, 8, hipMemcpyDeviceToHost, s));
-        GS_TRY(hipStreamSynchronize(s));
-        if (errs) return fail_out();   // a sort permutation out of range
+        HIP_RET(hipMemcpyAsync(host.data() + from, d_dst + from,
+                               (3 * N - from) * 8, hipMemcpyDeviceToHost, s));
+        HIP_RET(hipMemcpyAsync(pv->bitmap.data(), d_bm, bm_words * 8,
+                               hipMemcpyDeviceToHost, s));
+        HIP_RET(hipMemcpyAsync(pv->n_valid.data(), d_nv, n_groups * 4,
+                               hipMemcpyDeviceToHost, s));
+        HIP_RET(hipMemcpyAsync(&errs, d_err, 8, hipMemcpyDeviceToHost, s));
+        HIP_RET(hipStreamSynchronize(s));
+        if (errs) return hipErrorUnknown;   // a sort permutation out of range
         std::memcpy(pv->packed.data(), host.data() + 2 * N, N * 8);
     } else {
-        GS_TRY(hx::launch_gather_multi(s, srcs, 3, pc, d_dst, (uint32_t)N));
+        HIP_RET(hx::launch_gather_multi(s, srcs, 3, pc, d_dst, (uint32_t)N));
         if (!streams) {   // with streams the three columns stay on the device
-            GS_TRY(hipMemcpyAsync(host.data(), d_dst, 3 * N * 8,
-                                  hipMemcpyDeviceToHost, s));
-            GS_TRY(hipStreamSynchronize(s));
+            HIP_RET(hipMemcpyAsync(host.data(), d_dst, 3 * N * 8,
+                                   hipMemcpyDeviceToHost, s));
+            HIP_RET(hipStreamSynchronize(s));
             std::memcpy(v2.data(), host.data() + 2 * N, N * 8);
         }
     }
@@ -2860,17 +2992,14 @@ static bool gpu_sort_batch(const uint64_t* series, const int64_t* ts,
         // the OPTIONAL value page opens with its level block: host twin
         const int64_t col_words[5] = {0, (int64_t)N, pv ? -1 : 2 * (int64_t)N,
                                       -1, -1};
-        GS_TRY(compress_columns_device(s, (const uint8_t*)d_dst, col_words,
-                                       (uint32_t)N, nullptr, *streams));
+        HIP_RET(compress_columns_device(s, (const uint8_t*)d_dst, col_words,
+                                        (uint32_t)N, nullptr, *streams));
     }
-#undef GS_TRY
     if (!streams) {
         std::memcpy(s2.data(), host.data(), N * 8);
         std::memcpy(t2.data(), host.data() + N, N * 8);
     }
-    if (d_temp) (void)hipFree(d_temp);
-    (void)hipFree(dev);
-    return true;
+    return hipSuccess;
 }
 
 // hx_write and hx_write_nullable. validity: LSB-first bitmap over the batch
@@ -2883,7 +3012,7 @@ static hx_status write_batch(hx_handle* h, const uint64_t* series,
     // ColumnarStorage::write (storage.rs:76-89, :307-333): sort the batch by
     // primary key (sort_batch, storage.rs:244-256 — GPU radix sort when a
     // device is visible, the reference's CPU SortExec otherwise is NOT
-    // mirrored: ingest prep stays host-side std::stable_sort in that case),
+    // mirrored: ingest prep stays a host-side stable sort in that case),
     // allocate the file id (= sequence, sst.rs:39-46), write one SST,
     // add it to the catalog (manifest add_file, manifest/mod.rs:115-157).
     if (!h || !series || !ts || !value || n <= 0 || !out_seq)
@@ -2899,22 +3028,10 @@ static hx_status write_batch(hx_handle* h, const uint64_t* series,
                     "a bytes write codec is set (hx_set_bytes_write_codec): "
                     "the handle writes a Binary value column");
     if (enable_check) {
-        // segment-crossing check (storage.rs:309-316). The reference uses
-        // Rust truncating division on start/seg vs (end-1)/seg, where end
-        // is the exclusive max; mirror that exactly (C++ `/` truncates the
-        // same way), so negative-timestamp writes agree with the reference.
-        int64_t mn = ts[0], mx = ts[0];
-        for (int64_t i = 1; i < n; i++) {
-            mn = std::min(mn, ts[i]);
-            mx = std::max(mx, ts[i]);
-        }
-        if (mn / h->segment_ms != mx / h->segment_ms)
-            return fail(HX_ERR_INVALID,
-                        "write crosses a segment boundary (storage.rs:309-316)");
+        hx_status st = check_segment(h, ts, n);
+        if (st != HX_OK) return st;
     }
-    // stable sort by (series, ts) — equal PKs keep batch order
-    // (LastValueOperator's last-wins depends on it, operator.rs:37-44).
-    // Large batches sort on the GPU (rocPRIM LSD radix, stable): the
+    // stable sort by (series, ts). Large batches sort on the GPU (rocPRIM LSD radix, stable): the
     // ingest-side analog of sort_batch's SortExec (storage.rs:244-256) —
     // SURVEY §8(f) row 3's sort half. Small batches (or no device) stay
     // on the host.
@@ -2931,38 +3048,23 @@ static hx_status write_batch(hx_handle* h, const uint64_t* series,
                              // the writer compresses with the host twin
     bool sorted_on_gpu = false;
     if (n >= (1 << 16) && hip_device_count() > 0) {
-        sorted_on_gpu = gpu_sort_batch(series, ts, value, n, s2, t2, v2,
-                                       validity, nullable ? &pv : nullptr,
-                                       codec ? &streams : nullptr);
+        sorted_on_gpu =
+            gpu_sort_batch(series, ts, value, n, s2, t2, v2, validity,
+                           nullable ? &pv : nullptr,
+                           codec ? &streams : nullptr) == hipSuccess;
         if (!sorted_on_gpu) streams = DeviceStreams();
     }
     if (!sorted_on_gpu) {
-        std::vector<uint32_t> order(n);
-        for (int64_t i = 0; i < n; i++) order[i] = (uint32_t)i;
-        std::stable_sort(order.begin(), order.end(),
-                         [&](uint32_t a2, uint32_t b2) {
-                             if (series[a2] != series[b2])
-                                 return series[a2] < series[b2];
-                             return ts[a2] < ts[b2];
-                         });
+        const std::vector<uint32_t> order = host_pk_order(series, ts, n);
         for (int64_t i = 0; i < n; i++) {
             s2[i] = series[order[i]];
             t2[i] = ts[order[i]];
             v2[i] = value[order[i]];
         }
-        if (nullable) {
-            pv.resize(n, kRowGroup);
-            hx::pack_optional_host((const uint64_t*)value, validity,
-                                   order.data(), (uint64_t)n, (uint64_t)n,
-                                   (uint64_t)kRowGroup, pv.packed.data(),
-                                   pv.bitmap.data(), pv.n_valid.data());
-        }
+        if (nullable)
+            pv.pack_host(value, validity, order.data(), n, kRowGroup);
     }
-    uint64_t max_seq = 0;
-    for (const auto& s : h->ssts) max_seq = std::max(max_seq, s.seq);
-    const uint64_t new_seq = max_seq + 1;
-    std::string out_path = h->store + "/data/" + std::to_string(new_seq) +
-                           ".sst";
+    const NewSst out = next_sst(h);
     const hx::PagePayload* ready =
         streams.ready.empty() ? nullptr : streams.ready.data();
     // a column kernel 1e compressed never came to the host: its pages and
@@ -2971,17 +3073,15 @@ static hx_status write_batch(hx_handle* h, const uint64_t* series,
     const int64_t* w_ts = streams.on_device[1] ? nullptr : t2.data();
     const double* w_value = streams.on_device[2] ? nullptr : v2.data();
     std::string werr =
-        nullable ? hx::write_metric_sst_nullable(out_path, w_series, w_ts,
-                                                 pv.view(), nullptr, new_seq,
+        nullable ? hx::write_metric_sst_nullable(out.path, w_series, w_ts,
+                                                 pv.view(), nullptr, out.seq,
                                                  n, kRowGroup, codec, ready)
-                 : hx::write_metric_sst(out_path, w_series, w_ts, w_value,
-                                        new_seq, n, kRowGroup, codec, ready);
+                 : hx::write_metric_sst(out.path, w_series, w_ts, w_value,
+                                        out.seq, n, kRowGroup, codec, ready);
     if (!werr.empty()) return fail(HX_ERR_IO, werr);
-    CatSst fresh;
-    hx_status st = read_file_meta(out_path, new_seq, fresh);
+    hx_status st = catalog_add(h, out);
     if (st != HX_OK) return st;
-    h->ssts.push_back(std::move(fresh));
-    *out_seq = new_seq;
+    *out_seq = out.seq;
     return HX_OK;
 }
 
@@ -3010,267 +3110,6 @@ extern "C" hx_status hx_write_nullable(hx_handle* h, const uint64_t* series,
     }
     return write_batch(h, series, ts, value, validity, n, enable_check,
                        out_seq);
-}
-
-// The shared body of hx_compact and hx_compact_files, from the prepared plan
-// to the catalog update: filter + dedup into a row stream, two stable sort
-// passes (ts, then series), gather by the final permutation, one D2H, the
-// native writer, then add-before-delete. keep_seq: the rows keep their own
-// __seq__ (hx_compact_files); otherwise the file carries the fresh id.
-// Writer setting 1 (hx_set_nullable_values): null values survive. The scan
-// emits one validity word per row when the plan staged a null; series, ts
-// (and seq) are gathered as before and kernel 1d packs the values per output
-// row group by the same permutation, so the host receives packed values,
-// bitmaps and counts, never the 8-byte validity words.
-static hx_status finish_compaction(hx_handle* h, const std::string& out_path,
-                                   uint64_t new_seq,
-                                   const std::vector<char>& in_set,
-                                   uint64_t* out_new_seq);
-static hx_status compact_rows_bytes(hx_handle* h, hx_prepared* P,
-                                    const std::vector<char>& in_set,
-                                    uint64_t max_seq, bool keep_seq,
-                                    uint64_t* out_new_seq);
-
-static hx_status compact_rows(hx_handle* h, hx_prepared* P,
-                              const std::vector<char>& in_set,
-                              uint64_t max_seq, bool keep_seq,
-                              uint64_t* out_new_seq) {
-    // Binary value column: the value words are handles, not values
-    if (h->bytes_value)
-        return compact_rows_bytes(h, P, in_set, max_seq, keep_seq,
-                                  out_new_seq);
-    DevPlan& plan = P->plans[0];
-    const bool nullable = h->nullable_values != 0;
-    const int32_t codec = h->write_codec;
-    // the REQUIRED writer cannot keep a null: dropping it would be data
-    // loss. Refused before anything is written or unlinked.
-    if (plan.has_nulls && !nullable)
-        return fail(HX_ERR_UNSUPPORTED,
-                    "compaction inputs hold null values (the native writer "
-                    "writes REQUIRED columns)");
-    HIP_TRY(hipSetDevice(plan.device));
-    hipStream_t s = plan.stream;
-    hx_status st = ensure_decoded(plan, s);
-    if (st != HX_OK) return st;
-
-    const uint64_t cap = (uint64_t)plan.rows_scanned;
-    if (cap == 0) return HX_OK;
-    if (cap > 0xFFFFFFFFull)
-        return fail(HX_ERR_UNSUPPORTED,
-                    "row streams above 2^32 rows per call: split the range");
-    const bool nulls = plan.has_nulls;
-    const uint32_t n_cols = keep_seq ? 4 : 3;
-    size_t need = cap * 8 * (n_cols + 2 + (nulls ? 1 : 0)) + cap * 4 * 3 + 64;
-    st = ensure_dev(&plan.d_scratch, &plan.scratch_cap, need);
-    if (st != HX_OK) return st;
-    uint8_t* base = (uint8_t*)plan.d_scratch;
-    auto carve8 = [&](size_t count) {
-        uint8_t* p = base;
-        base += (count * 8 + 7) & ~size_t(7);
-        return p;
-    };
-    uint64_t* d_series = (uint64_t*)carve8(cap);
-    long long* d_ts = (long long*)carve8(cap);
-    double* d_val = (double*)carve8(cap);
-    uint64_t* d_seq = keep_seq ? (uint64_t*)carve8(cap) : nullptr;
-    uint64_t* d_keys = (uint64_t*)carve8(cap);
-    uint64_t* d_keys_out = (uint64_t*)carve8(cap);
-    unsigned long long* d_cursor = (unsigned long long*)carve8(1);
-    uint32_t* perm_a = (uint32_t*)base; base += cap * 4;
-    uint32_t* perm_b = (uint32_t*)base; base += cap * 4;
-    uint32_t* perm_c = (uint32_t*)base; base += cap * 4;
-    // one 0/1 word per surviving row (behind the perms, 8-aligned)
-    base = (uint8_t*)(((uintptr_t)base + 7) & ~uintptr_t(7));
-    uint64_t* d_valid = nulls ? (uint64_t*)carve8(cap) : nullptr;
-
-    HIP_TRY(hipMemsetAsync(d_cursor, 0, 8, s));
-    hx::AggParams A = base_params(P, plan);
-    HIP_TRY(hx::launch_scan_rows(s, A, 0, A.n_rgs, d_series, d_ts, d_val,
-                                 d_cursor, cap, d_seq, 0, d_valid));
-    unsigned long long n64 = 0;
-    HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(hipMemcpy(&n64, d_cursor, 8, hipMemcpyDeviceToHost));
-    if (n64 > cap) return fail(HX_ERR_HIP, "compact row buffer overflow");
-    const uint32_t n = (uint32_t)n64;
-    if (n == 0) return HX_OK;
-
-    HIP_TRY(hx::launch_iota(s, perm_a, n));
-    HIP_TRY(hx::launch_gather_u64(s, (const unsigned long long*)d_ts, perm_a,
-                                  (unsigned long long*)d_keys, n));
-    HIP_TRY(hx::launch_xor_sign(s, (unsigned long long*)d_keys, n));
-    HIP_TRY(hx::sort_pairs_u64(s, d_keys, d_keys_out, perm_a, perm_b, n,
-                               &plan.d_sort_temp, &plan.sort_temp_cap));
-    HIP_TRY(hx::launch_gather_u64(s, (const unsigned long long*)d_series,
-                                  perm_b, (unsigned long long*)d_keys, n));
-    HIP_TRY(hx::sort_pairs_u64(s, d_keys, d_keys_out, perm_b, perm_c, n,
-                               &plan.d_sort_temp, &plan.sort_temp_cap));
-    const uint32_t* perm = perm_c;
-
-    // gather destination, one D2H: series, ts, value [, seq]; the nullable
-    // form has the packed values in the value slot and the bitmaps, counts
-    // and the error count behind the columns
-    const size_t n_groups = (size_t(n) + kRowGroup - 1) / kRowGroup;
-    const size_t bm_words = n_groups * size_t(kRowGroup / 64);
-    const size_t nv_words = (n_groups + 1) / 2;   // u32 counts, in 8-byte units
-    const size_t words = size_t(n_cols) * n +
-                         (nullable ? bm_words + nv_words + 1 : 0);
-    // under Snappy without the nullable form nothing comes back raw
-    std::vector<uint64_t> host(!codec || nullable ? words : 0);
-    unsigned long long* d_dst = nullptr;
-    HIP_TRY(hipMalloc((void**)&d_dst, words * 8));
-    std::unique_ptr<void, void (*)(void*)> dst_guard(
-        d_dst, [](void* q) { (void)hipFree(q); });
-    // HX_DEBUG: HIP-event times of the final gather, of kernel 1d and of
-    // kernel 1e with its pack pass
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    const bool timed = getenv("HX_DEBUG") != nullptr;
-    struct EvGuard {
-        hipEvent_t* e;
-        ~EvGuard() {
-            for (int i = 0; i < 4; i++)
-                if (e[i]) (void)hipEventDestroy(e[i]);
-        }
-    } ev_guard{ev};
-    if (timed) {
-        for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
-        HIP_TRY(hipEventRecord(ev[0], s));
-    }
-    if (nullable) {
-        // slots 0 and 1 by the gather, slot 2 by the pack kernel, slot 3
-        // (seq) by a gather of its own
-        unsigned long long* d_bm = d_dst + size_t(n_cols) * n;
-        unsigned long long* d_nv = d_bm + bm_words;
-        unsigned long long* d_err = d_nv + nv_words;
-        HIP_TRY(hipMemsetAsync(d_err, 0, 8, s));
-        const unsigned long long* srcs[2] = {
-            (const unsigned long long*)d_series,
-            (const unsigned long long*)d_ts};
-        HIP_TRY(hx::launch_gather_multi(s, srcs, 2, perm, d_dst, n));
-        if (keep_seq)
-            HIP_TRY(hx::launch_gather_u64(
-                s, (const unsigned long long*)d_seq, perm,
-                d_dst + 3 * size_t(n), n));
-        if (timed) HIP_TRY(hipEventRecord(ev[1], s));
-        HIP_TRY(hx::launch_pack_optional(
-            s, (const unsigned long long*)d_val, d_valid, false, perm, n, n,
-            (uint32_t)kRowGroup, d_dst + 2 * size_t(n), (uint64_t*)d_bm,
-            (uint32_t*)d_nv, d_err));
-    } else {
-        const unsigned long long* srcs[4] = {
-            (const unsigned long long*)d_series,
-            (const unsigned long long*)d_ts,
-            (const unsigned long long*)d_val,
-            (const unsigned long long*)d_seq};
-        HIP_TRY(hx::launch_gather_multi(s, srcs, n_cols, perm, d_dst, n));
-        if (timed) HIP_TRY(hipEventRecord(ev[1], s));
-    }
-    if (timed) HIP_TRY(hipEventRecord(ev[2], s));
-    // Writer codec Snappy: kernel 1e over the 8192-row slices of the columns
-    // where they sit in d_dst (series, ts, per-row seq, and value in its
-    // REQUIRED form; an OPTIONAL value page opens with its level block and
-    // goes through the host twin), then scan-and-pack and one D2H of the
-    // streams. Codec 0 launches nothing here.
-    DeviceStreams streams;
-    if (codec) {
-        const int64_t col_words[5] = {
-            0, (int64_t)n, nullable ? -1 : 2 * (int64_t)n,
-            keep_seq ? 3 * (int64_t)n : -1, -1};
-        HIP_TRY(compress_columns_device(s, (const uint8_t*)d_dst, col_words,
-                                        n, timed ? ev[3] : nullptr, streams));
-    } else if (timed) {
-        HIP_TRY(hipEventRecord(ev[3], s));
-    }
-    // what still has to come back raw: everything under codec 0; under
-    // Snappy only what kernel 1e did not take — the packed values and, behind
-    // the columns, the bitmaps, counts and error word of the nullable form
-    size_t raw_bytes = 0;
-    auto bring = [&](size_t w0, size_t w1) {
-        raw_bytes += (w1 - w0) * 8;
-        return hipMemcpyAsync(host.data() + w0, d_dst + w0, (w1 - w0) * 8,
-                              hipMemcpyDeviceToHost, s);
-    };
-    if (!codec) {
-        HIP_TRY(bring(0, words));
-    } else if (nullable) {
-        HIP_TRY(bring(2 * size_t(n), 3 * size_t(n)));
-        HIP_TRY(bring(size_t(n_cols) * n, words));
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-    dst_guard.reset();
-    if (timed) {
-        float gather_ms = 0, pack_ms = 0, comp_ms = 0;
-        HIP_TRY(hipEventElapsedTime(&gather_ms, ev[0], ev[1]));
-        HIP_TRY(hipEventElapsedTime(&pack_ms, ev[1], ev[2]));
-        HIP_TRY(hipEventElapsedTime(&comp_ms, ev[2], ev[3]));
-        fprintf(stderr,
-                "[hx] compact rows=%u cols_gathered=%u nullable=%d nulls=%d "
-                "codec=%d gather_ms=%.4f pack_ms=%.4f comp_ms=%.4f "
-                "d2h_bytes=%zu\n",
-                n, nullable ? n_cols - 1 : n_cols, int(nullable), int(nulls),
-                codec, gather_ms, pack_ms, comp_ms,
-                raw_bytes + streams.d2h_bytes);
-    }
-    const hx::PagePayload* ready =
-        streams.ready.empty() ? nullptr : streams.ready.data();
-
-    const uint64_t new_seq = max_seq + 1;  // fresh file id (sst.rs:39-46)
-    std::string out_path = h->store + "/data/" + std::to_string(new_seq) +
-                           ".sst";
-    // a column kernel 1e compressed never came to the host (null here): its
-    // pages and statistics are in `ready`
-    const uint64_t* h_series = streams.on_device[0] ? nullptr : host.data();
-    const int64_t* h_ts =
-        streams.on_device[1] ? nullptr : (const int64_t*)(host.data() + n);
-    const uint64_t* h_val =
-        streams.on_device[2] ? nullptr : host.data() + 2 * size_t(n);
-    const uint64_t* h_seq = keep_seq && !streams.on_device[3]
-                                ? host.data() + 3 * size_t(n) : nullptr;
-    std::string werr;
-    if (nullable) {
-        const uint64_t* h_bm = host.data() + size_t(n_cols) * n;
-        if (h_bm[bm_words + nv_words] != 0)
-            return fail(HX_ERR_HIP, "compact: sort permutation out of range");
-        hx::NullableValues nv{h_val, h_bm,
-                              (const uint32_t*)(h_bm + bm_words)};
-        werr = hx::write_metric_sst_nullable(out_path, h_series, h_ts, nv,
-                                             h_seq, new_seq, n, kRowGroup,
-                                             codec, ready);
-    } else if (keep_seq) {
-        werr = hx::write_metric_sst_seqs(out_path, h_series, h_ts,
-                                         (const double*)h_val, h_seq, n,
-                                         kRowGroup, codec, ready);
-    } else {
-        werr = hx::write_metric_sst(out_path, h_series, h_ts,
-                                    (const double*)h_val, new_seq, n,
-                                    kRowGroup, codec, ready);
-    }
-    if (!werr.empty()) return fail(HX_ERR_IO, werr);
-    return finish_compaction(h, out_path, new_seq, in_set, out_new_seq);
-}
-
-// catalog update: add new file, drop + unlink inputs (add-before-delete,
-// executor.rs:206-220)
-static hx_status finish_compaction(hx_handle* h, const std::string& out_path,
-                                   uint64_t new_seq,
-                                   const std::vector<char>& in_set,
-                                   uint64_t* out_new_seq) {
-    CatSst fresh;
-    hx_status st = read_file_meta(out_path, new_seq, fresh);
-    if (st != HX_OK) return st;
-    std::vector<CatSst> kept;
-    for (size_t i = 0; i < h->ssts.size(); i++) {
-        if (in_set[i]) {
-            unlink(h->ssts[i].path.c_str());  // best-effort, like the reference
-            continue;
-        }
-        kept.push_back(std::move(h->ssts[i]));
-    }
-    kept.push_back(std::move(fresh));
-    std::sort(kept.begin(), kept.end(),
-              [](const CatSst& a, const CatSst& b) { return a.seq < b.seq; });
-    h->ssts = std::move(kept);
-    *out_new_seq = new_seq;
-    return HX_OK;
 }
 
 // ---------------------------------------------------------------------------
@@ -3306,19 +3145,6 @@ bool ba_debug_args_ok(const uint8_t* src, uint64_t src_size,
            row_group <= hx::BA_MAX_ROW_GROUP && (!n_src || handles) &&
            (!src_size || src);
 }
-
-struct DevBufs {
-    std::vector<void*> p;
-    ~DevBufs() {
-        for (void* q : p)
-            if (q) (void)hipFree(q);
-    }
-    hipError_t alloc(void** out, size_t bytes) {
-        hipError_t e = hipMalloc(out, bytes ? bytes : 1);
-        if (e == hipSuccess) p.push_back(*out);
-        return e;
-    }
-};
 
 // The size pass of kernel 1f with its device buffers, and what the caller
 // must refuse before anything is written: rows the kernel refused, Append
@@ -3556,19 +3382,10 @@ hipError_t compress_ba_pages_device(hipStream_t s, const uint8_t* d_image,
     const size_t stat_bytes = size_t(n_pages) * sizeof(hx::BaPageStat);
     const size_t back_bytes = len_bytes + 8 + stat_bytes;
     uint8_t* dev = nullptr;
-    hipError_t e = hipMalloc((void**)&dev, 2 * slot_bytes + desc_bytes +
-                                               off_bytes + back_bytes);
-    if (e != hipSuccess) return e;
-    std::unique_ptr<void, void (*)(void*)> guard(
-        dev, [](void* q) { (void)hipFree(q); });
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    struct EvGuard {
-        hipEvent_t* e;
-        ~EvGuard() {
-            for (int i = 0; i < 3; i++)
-                if (e[i]) (void)hipEventDestroy(e[i]);
-        }
-    } ev_guard{ev};
+    DevBufs bufs;
+    HIP_RET(bufs.alloc((void**)&dev, 2 * slot_bytes + desc_bytes + off_bytes +
+                                         back_bytes));
+    HipEvents<3> ev;
     uint8_t* d_slots = dev;
     uint8_t* d_packed = dev + slot_bytes;
     auto* d_descs = (hx::SnappyCompDesc*)(d_packed + slot_bytes);
@@ -3577,26 +3394,24 @@ hipError_t compress_ba_pages_device(hipStream_t s, const uint8_t* d_image,
     unsigned long long* d_err =
         (unsigned long long*)((uint8_t*)d_lens + len_bytes);
     hx::BaPageStat* d_stats = (hx::BaPageStat*)(d_err + 1);
-#define BS_TRY(x) do { e = (x); if (e != hipSuccess) return e; } while (0)
-    if (timed)
-        for (auto& v : ev) BS_TRY(hipEventCreate(&v));
-    BS_TRY(hipMemcpyAsync(d_descs, descs.data(),
-                          size_t(n_descs) * sizeof(descs[0]),
-                          hipMemcpyHostToDevice, s));
-    BS_TRY(hipMemsetAsync(d_err, 0, 8, s));
-    if (timed) BS_TRY(hipEventRecord(ev[0], s));
-    BS_TRY(hx::launch_ba_page_minmax(s, d_image, d_page_off, d_row_len, n_out,
-                                     (uint32_t)kRowGroup, d_stats));
-    if (timed) BS_TRY(hipEventRecord(ev[1], s));
-    BS_TRY(hx::launch_snappy_compress(s, d_image, d_slots, d_descs, n_descs,
-                                      d_lens, d_err));
-    BS_TRY(hx::launch_snappy_pack(s, d_slots, d_descs, n_descs, d_lens,
-                                  d_offs, d_packed));
-    if (timed) BS_TRY(hipEventRecord(ev[2], s));
+    if (timed) HIP_RET(ev.create());
+    HIP_RET(hipMemcpyAsync(d_descs, descs.data(),
+                           size_t(n_descs) * sizeof(descs[0]),
+                           hipMemcpyHostToDevice, s));
+    HIP_RET(hipMemsetAsync(d_err, 0, 8, s));
+    if (timed) HIP_RET(hipEventRecord(ev[0], s));
+    HIP_RET(hx::launch_ba_page_minmax(s, d_image, d_page_off, d_row_len, n_out,
+                                      (uint32_t)kRowGroup, d_stats));
+    if (timed) HIP_RET(hipEventRecord(ev[1], s));
+    HIP_RET(hx::launch_snappy_compress(s, d_image, d_slots, d_descs, n_descs,
+                                       d_lens, d_err));
+    HIP_RET(hx::launch_snappy_pack(s, d_slots, d_descs, n_descs, d_lens,
+                                   d_offs, d_packed));
+    if (timed) HIP_RET(hipEventRecord(ev[2], s));
     std::vector<uint64_t> back((back_bytes + 7) / 8);
-    BS_TRY(hipMemcpyAsync(back.data(), d_lens, back_bytes,
-                          hipMemcpyDeviceToHost, s));
-    BS_TRY(hipStreamSynchronize(s));
+    HIP_RET(hipMemcpyAsync(back.data(), d_lens, back_bytes,
+                           hipMemcpyDeviceToHost, s));
+    HIP_RET(hipStreamSynchronize(s));
     if (back[len_bytes / 8] != 0) return hipErrorUnknown;
     std::memcpy(out.lens.data(), back.data(), size_t(n_descs) * 4);
     std::memcpy(out.stats.data(), (const uint8_t*)back.data() + len_bytes + 8,
@@ -3604,14 +3419,13 @@ hipError_t compress_ba_pages_device(hipStream_t s, const uint8_t* d_image,
     size_t total = 0;
     for (uint32_t p = 0; p < n_descs; p++) total += out.lens[p];
     out.bytes.resize(total);
-    BS_TRY(hipMemcpyAsync(out.bytes.data(), d_packed, total,
-                          hipMemcpyDeviceToHost, s));
-    BS_TRY(hipStreamSynchronize(s));
+    HIP_RET(hipMemcpyAsync(out.bytes.data(), d_packed, total,
+                           hipMemcpyDeviceToHost, s));
+    HIP_RET(hipStreamSynchronize(s));
     if (timed) {
-        BS_TRY(hipEventElapsedTime(&out.stats_ms, ev[0], ev[1]));
-        BS_TRY(hipEventElapsedTime(&out.compress_ms, ev[1], ev[2]));
+        HIP_RET(hipEventElapsedTime(&out.stats_ms, ev[0], ev[1]));
+        HIP_RET(hipEventElapsedTime(&out.compress_ms, ev[1], ev[2]));
     }
-#undef BS_TRY
     out.d2h_bytes = back_bytes + total;
     return hipSuccess;
 }
@@ -3887,12 +3701,7 @@ static hx_status gpu_write_bytes(const uint64_t* series, const int64_t* ts,
     hipStream_t s = nullptr;
     const size_t N = (size_t)n;
     DevBufs dev;
-    void* d_temp = nullptr;
-    size_t temp_cap = 0;
-    struct TempGuard {
-        void** t;
-        ~TempGuard() { if (*t) (void)hipFree(*t); }
-    } temp_guard{&d_temp};
+    SortTemp temp;
     uint64_t *d_series, *d_ts, *d_h, *d_ka, *d_kb, *d_hs;
     uint32_t *pa, *pb, *pc;
     uint8_t *d_bytes, *d_final;
@@ -3914,7 +3723,7 @@ static hx_status gpu_write_bytes(const uint64_t* series, const int64_t* ts,
         HIP_TRY(hipMemcpyAsync(d_bytes, bytes, n_bytes, hipMemcpyHostToDevice,
                                s));
     HIP_TRY(ingest_sort_perm(s, d_series, (const int64_t*)d_ts, d_ka, d_kb,
-                             pa, pb, pc, N, &d_temp, &temp_cap));
+                             pa, pb, pc, N, &temp.p, &temp.cap));
     HIP_TRY(hx::launch_gather_u64(s, (const unsigned long long*)d_h, pc,
                                   (unsigned long long*)d_hs, (uint32_t)N));
     BaPageBuilder b;
@@ -3980,14 +3789,8 @@ extern "C" hx_status hx_write_bytes(hx_handle* h, const uint64_t* series,
     if (!bytes && offsets[n] != offsets[0])
         return fail(HX_ERR_INVALID, "bad argument");
     if (enable_check) {
-        int64_t mn = ts[0], mx = ts[0];
-        for (int64_t i = 1; i < n; i++) {
-            mn = std::min(mn, ts[i]);
-            mx = std::max(mx, ts[i]);
-        }
-        if (mn / h->segment_ms != mx / h->segment_ms)
-            return fail(HX_ERR_INVALID,
-                        "write crosses a segment boundary (storage.rs:309-316)");
+        st = check_segment(h, ts, n);
+        if (st != HX_OK) return st;
     }
     // handles relative to bytes + offsets[0]
     const uint8_t* src = bytes ? bytes + offsets[0] : nullptr;
@@ -4013,14 +3816,7 @@ extern "C" hx_status hx_write_bytes(hx_handle* h, const uint64_t* series,
                              on_device ? &value_streams : nullptr);
         if (st != HX_OK) return st;
     } else {
-        std::vector<uint32_t> order(n);
-        for (int64_t i = 0; i < n; i++) order[i] = (uint32_t)i;
-        std::stable_sort(order.begin(), order.end(),
-                         [&](uint32_t a2, uint32_t b2) {
-                             if (series[a2] != series[b2])
-                                 return series[a2] < series[b2];
-                             return ts[a2] < ts[b2];
-                         });
+        const std::vector<uint32_t> order = host_pk_order(series, ts, n);
         std::vector<uint64_t> hs(n);
         for (int64_t i = 0; i < n; i++) hs[i] = handles[order[i]];
         const uint64_t n_pages = hx::ba_n_pages(N, kRowGroup);
@@ -4053,11 +3849,7 @@ extern "C" hx_status hx_write_bytes(hx_handle* h, const uint64_t* series,
                             (uint32_t)n_pages, row_len.data(), N, cuts,
                             value_streams);
     }
-    uint64_t max_seq = 0;
-    for (const auto& s : h->ssts) max_seq = std::max(max_seq, s.seq);
-    const uint64_t new_seq = max_seq + 1;
-    std::string out_path = h->store + "/data/" + std::to_string(new_seq) +
-                           ".sst";
+    const NewSst out = next_sst(h);
     const uint32_t n_pages32 = (uint32_t)(page_off.size() - 1);
     std::vector<hx::PagePayload> ready;
     if (codec == HX_CODEC_SNAPPY) {
@@ -4070,102 +3862,40 @@ extern "C" hx_status hx_write_bytes(hx_handle* h, const uint64_t* series,
                          cuts);
     }
     std::string werr = hx::write_metric_sst_bytes(
-        out_path, on_device ? nullptr : (const uint64_t*)host.data(),
+        out.path, on_device ? nullptr : (const uint64_t*)host.data(),
         on_device ? nullptr : (const int64_t*)(host.data() + N * 8), nullptr,
-        nullptr, nullptr, new_seq, n, kRowGroup, ready.data(), codec);
+        nullptr, nullptr, out.seq, n, kRowGroup, ready.data(), codec);
     if (!werr.empty()) return fail(HX_ERR_IO, werr);
-    CatSst fresh;
-    st = read_file_meta(out_path, new_seq, fresh);
+    st = catalog_add(h, out);
     if (st != HX_OK) return st;
     h->bytes_value = true;
-    h->ssts.push_back(std::move(fresh));
-    *out_seq = new_seq;
+    *out_seq = out.seq;
     return HX_OK;
 }
 
 // compact_rows for a Binary value column. The row stream's value words are
 // handles into the staged blob. Overwrite: survivors as the f64 path (last
-// wins), the winner's handle. Append: every row is kept, a leading stable
-// pass on the packed (seq << 32 | file row) key exactly as hx_scan runs it,
-// then ts, then series; equal-PK runs become ONE output row whose value is
-// the concatenation in that order and whose sequence (keep_seq) is that of
-// the run's FIRST row (BytesMergeOperator takes element 0 of every non-value
-// column, operator.rs:99-102, and under keep_builtin __seq__ is one). Kernel
-// 1f builds the page images from the blob; value bytes never cross PCIe as
-// rows: one D2H of the output rows' key columns and the page images.
+// wins), the winner's handle. Append: the stream keeps every row, equal-PK
+// rows in ascending sequence order, exactly as hx_scan sees it; equal-PK runs
+// become ONE output row whose value is the concatenation in that order and
+// whose sequence (keep_seq) is that of the run's FIRST row (BytesMergeOperator
+// takes element 0 of every non-value column, operator.rs:99-102, and under
+// keep_builtin __seq__ is one). Kernel 1f builds the page images from the
+// blob; value bytes never cross PCIe as rows: one D2H of the output rows' key
+// columns and the page images.
 static hx_status compact_rows_bytes(hx_handle* h, hx_prepared* P,
                                     const std::vector<char>& in_set,
-                                    uint64_t max_seq, bool keep_seq,
-                                    uint64_t* out_new_seq) {
+                                    bool keep_seq, uint64_t* out_new_seq) {
     DevPlan& plan = P->plans[0];
     const bool append = h->update_mode == 1;
-    if (append)
-        for (const auto& c : h->ssts)
-            if (c.seq >= (1ull << 32))
-                return fail(HX_ERR_UNSUPPORTED,
-                            "append stores need file sequences < 2^32");
-    HIP_TRY(hipSetDevice(plan.device));
-    hipStream_t s = plan.stream;
-    hx_status st = ensure_decoded(plan, s);
+    RowStream rs;
+    hx_status st =
+        sorted_row_stream(h, P, plan, keep_seq, append, "compact", rs);
     if (st != HX_OK) return st;
-    const uint64_t cap = (uint64_t)plan.rows_scanned;
-    if (cap == 0) return HX_OK;
-    if (cap > 0xFFFFFFFFull)
-        return fail(HX_ERR_UNSUPPORTED,
-                    "row streams above 2^32 rows per call: split the range");
-    const bool want_seq = keep_seq || append;
-    size_t need = cap * 8 * (5 + (want_seq ? 1 : 0)) + cap * 4 * 3 + 64;
-    st = ensure_dev(&plan.d_scratch, &plan.scratch_cap, need);
-    if (st != HX_OK) return st;
-    uint8_t* base = (uint8_t*)plan.d_scratch;
-    auto carve8 = [&](size_t count) {
-        uint8_t* p = base;
-        base += (count * 8 + 7) & ~size_t(7);
-        return p;
-    };
-    uint64_t* d_series = (uint64_t*)carve8(cap);
-    long long* d_ts = (long long*)carve8(cap);
-    double* d_val = (double*)carve8(cap);
-    uint64_t* d_seq = want_seq ? (uint64_t*)carve8(cap) : nullptr;
-    uint64_t* d_keys = (uint64_t*)carve8(cap);
-    uint64_t* d_keys_out = (uint64_t*)carve8(cap);
-    unsigned long long* d_cursor = (unsigned long long*)carve8(1);
-    uint32_t* perm_a = (uint32_t*)base; base += cap * 4;
-    uint32_t* perm_b = (uint32_t*)base; base += cap * 4;
-    uint32_t* perm_c = (uint32_t*)base; base += cap * 4;
-
-    HIP_TRY(hipMemsetAsync(d_cursor, 0, 8, s));
-    hx::AggParams A = base_params(P, plan);
-    A.keep_dups = append ? 1 : 0;
-    HIP_TRY(hx::launch_scan_rows(s, A, 0, A.n_rgs, d_series, d_ts, d_val,
-                                 d_cursor, cap, d_seq, append ? 1 : 0,
-                                 nullptr));
-    unsigned long long n64 = 0;
-    HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(hipMemcpy(&n64, d_cursor, 8, hipMemcpyDeviceToHost));
-    if (n64 > cap) return fail(HX_ERR_HIP, "compact row buffer overflow");
-    const uint32_t n = (uint32_t)n64;
+    const uint32_t n = rs.n;
     if (n == 0) return HX_OK;
-
-    HIP_TRY(hx::launch_iota(s, perm_a, n));
-    if (append) {
-        HIP_TRY(hx::launch_gather_u64(s, (const unsigned long long*)d_seq,
-                                      perm_a, (unsigned long long*)d_keys,
-                                      n));
-        HIP_TRY(hx::sort_pairs_u64(s, d_keys, d_keys_out, perm_a, perm_b, n,
-                                   &plan.d_sort_temp, &plan.sort_temp_cap));
-        std::swap(perm_a, perm_b);
-    }
-    HIP_TRY(hx::launch_gather_u64(s, (const unsigned long long*)d_ts, perm_a,
-                                  (unsigned long long*)d_keys, n));
-    HIP_TRY(hx::launch_xor_sign(s, (unsigned long long*)d_keys, n));
-    HIP_TRY(hx::sort_pairs_u64(s, d_keys, d_keys_out, perm_a, perm_b, n,
-                               &plan.d_sort_temp, &plan.sort_temp_cap));
-    HIP_TRY(hx::launch_gather_u64(s, (const unsigned long long*)d_series,
-                                  perm_b, (unsigned long long*)d_keys, n));
-    HIP_TRY(hx::sort_pairs_u64(s, d_keys, d_keys_out, perm_b, perm_c, n,
-                               &plan.d_sort_temp, &plan.sort_temp_cap));
-    const uint32_t* perm = perm_c;
+    hipStream_t s = plan.stream;
+    const uint32_t* perm = rs.perm;
 
     // sorted rows: series, ts, handle [, seq (Overwrite)]
     DevBufs dev;
@@ -4173,8 +3903,8 @@ static hx_status compact_rows_bytes(hx_handle* h, hx_prepared* P,
     unsigned long long* d_sorted = nullptr;
     HIP_TRY(dev.alloc((void**)&d_sorted, size_t(n_sorted) * n * 8));
     const unsigned long long* srcs[4] = {
-        (const unsigned long long*)d_series, (const unsigned long long*)d_ts,
-        (const unsigned long long*)d_val, (const unsigned long long*)d_seq};
+        (const unsigned long long*)rs.series, (const unsigned long long*)rs.ts,
+        (const unsigned long long*)rs.val, (const unsigned long long*)rs.seq};
     HIP_TRY(hx::launch_gather_multi(s, srcs, n_sorted, perm, d_sorted, n));
     const uint64_t* d_handles = (const uint64_t*)(d_sorted + 2 * size_t(n));
 
@@ -4195,7 +3925,7 @@ static hx_status compact_rows_bytes(hx_handle* h, hx_prepared* P,
         HIP_TRY(dev.alloc((void**)&d_nout, 8));
         HIP_TRY(hx::launch_group_heads(
             s, d_sorted, d_sorted + n,
-            keep_seq ? (const unsigned long long*)d_seq : nullptr, perm, n,
+            keep_seq ? (const unsigned long long*)rs.seq : nullptr, perm, n,
             d_flag, d_rank, d_gs, d_heads, d_heads + n,
             d_heads + 2 * size_t(n), d_nout, &plan.d_sort_temp,
             &plan.sort_temp_cap));
@@ -4212,16 +3942,9 @@ static hx_status compact_rows_bytes(hx_handle* h, hx_prepared* P,
 
     // HX_DEBUG: one event pair around the page-build launches
     const bool timed = getenv("HX_DEBUG") != nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    struct EvGuard {
-        hipEvent_t* e;
-        ~EvGuard() {
-            for (int i = 0; i < 2; i++)
-                if (e[i]) (void)hipEventDestroy(e[i]);
-        }
-    } ev_guard{ev};
+    HipEvents<2> ev;
     if (timed) {
-        for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
+        HIP_TRY(ev.create());
         HIP_TRY(hipEventRecord(ev[0], s));
     }
     BaPageBuilder b;
@@ -4247,9 +3970,7 @@ static hx_status compact_rows_bytes(hx_handle* h, hx_prepared* P,
         HIP_TRY(hipMemcpyAsync(d_final + k * size_t(n_out) * 8, keys[k],
                                size_t(n_out) * 8, hipMemcpyDeviceToDevice,
                                s));
-    const uint64_t new_seq = max_seq + 1;
-    std::string out_path = h->store + "/data/" + std::to_string(new_seq) +
-                           ".sst";
+    const NewSst out = next_sst(h);
     if (h->bytes_write_codec == HX_CODEC_SNAPPY) {
         // the image stays in HBM: statistics (kernel 1g) and streams (kernel
         // 1e) of the value pages, streams and statistics of the key columns;
@@ -4284,10 +4005,10 @@ static hx_status compact_rows_bytes(hx_handle* h, hx_prepared* P,
         std::vector<hx::PagePayload> ready = ks.ready;
         ba_ready_streams(ready, b.page_off.data(), b.n_pages, cuts, vs);
         std::string werr = hx::write_metric_sst_bytes(
-            out_path, nullptr, nullptr, nullptr, nullptr, nullptr, new_seq,
+            out.path, nullptr, nullptr, nullptr, nullptr, nullptr, out.seq,
             n_out, kRowGroup, ready.data(), HX_CODEC_SNAPPY);
         if (!werr.empty()) return fail(HX_ERR_IO, werr);
-        return finish_compaction(h, out_path, new_seq, in_set, out_new_seq);
+        return finish_compaction(h, out, in_set, out_new_seq);
     }
     std::vector<uint8_t> host(key_bytes + b.total());
     HIP_TRY(hipMemcpyAsync(host.data(), d_final, host.size(),
@@ -4310,11 +4031,201 @@ static hx_status compact_rows_bytes(hx_handle* h, hx_prepared* P,
         ba_ready(b.page_off.data(), b.n_pages, host.data() + key_bytes, cuts);
     const uint64_t* hk = (const uint64_t*)host.data();
     std::string werr = hx::write_metric_sst_bytes(
-        out_path, hk, (const int64_t*)(hk + n_out), nullptr, nullptr,
-        keep_seq ? hk + 2 * size_t(n_out) : nullptr, new_seq, n_out,
+        out.path, hk, (const int64_t*)(hk + n_out), nullptr, nullptr,
+        keep_seq ? hk + 2 * size_t(n_out) : nullptr, out.seq, n_out,
         kRowGroup, ready.data());
     if (!werr.empty()) return fail(HX_ERR_IO, werr);
-    return finish_compaction(h, out_path, new_seq, in_set, out_new_seq);
+    return finish_compaction(h, out, in_set, out_new_seq);
+}
+
+// The shared body of hx_compact and hx_compact_files, from the prepared plan
+// to the catalog update: the sorted row stream, a gather by its permutation,
+// one D2H, the native writer, then add-before-delete. keep_seq: the rows keep
+// their own __seq__ (hx_compact_files); otherwise the file carries the fresh
+// id. Writer setting 1 (hx_set_nullable_values): null values survive. The
+// stream has one validity word per row when the plan staged a null; series,
+// ts (and seq) are gathered as before and kernel 1d packs the values per
+// output row group by the same permutation, so the host receives packed
+// values, bitmaps and counts, never the 8-byte validity words.
+static hx_status compact_rows(hx_handle* h, hx_prepared* P,
+                              const std::vector<char>& in_set, bool keep_seq,
+                              uint64_t* out_new_seq) {
+    // Binary value column: the value words are handles, not values
+    if (h->bytes_value)
+        return compact_rows_bytes(h, P, in_set, keep_seq, out_new_seq);
+    DevPlan& plan = P->plans[0];
+    const bool nullable = h->nullable_values != 0;
+    const int32_t codec = h->write_codec;
+    // the REQUIRED writer cannot keep a null: dropping it would be data
+    // loss. Refused before anything is written or unlinked.
+    if (plan.has_nulls && !nullable)
+        return fail(HX_ERR_UNSUPPORTED,
+                    "compaction inputs hold null values (the native writer "
+                    "writes REQUIRED columns)");
+    RowStream rs;
+    hx_status st =
+        sorted_row_stream(h, P, plan, keep_seq, false, "compact", rs);
+    if (st != HX_OK) return st;
+    const uint32_t n = rs.n;
+    if (n == 0) return HX_OK;
+    hipStream_t s = plan.stream;
+    const bool nulls = rs.valid != nullptr;
+    const uint32_t n_cols = keep_seq ? 4 : 3;
+    const uint32_t* perm = rs.perm;
+
+    // gather destination, one D2H: series, ts, value [, seq]; the nullable
+    // form has the packed values in the value slot and the bitmaps, counts
+    // and the error count behind the columns
+    const size_t n_groups = (size_t(n) + kRowGroup - 1) / kRowGroup;
+    const size_t bm_words = n_groups * size_t(kRowGroup / 64);
+    const size_t nv_words = (n_groups + 1) / 2;   // u32 counts, in 8-byte units
+    const size_t words = size_t(n_cols) * n +
+                         (nullable ? bm_words + nv_words + 1 : 0);
+    // under Snappy without the nullable form nothing comes back raw
+    std::vector<uint64_t> host(!codec || nullable ? words : 0);
+    unsigned long long* d_dst = nullptr;
+    HIP_TRY(hipMalloc((void**)&d_dst, words * 8));
+    std::unique_ptr<void, void (*)(void*)> dst_guard(
+        d_dst, [](void* q) { (void)hipFree(q); });
+    // HX_DEBUG: HIP-event times of the final gather, of kernel 1d and of
+    // kernel 1e with its pack pass
+    HipEvents<4> ev;
+    const bool timed = getenv("HX_DEBUG") != nullptr;
+    if (timed) {
+        HIP_TRY(ev.create());
+        HIP_TRY(hipEventRecord(ev[0], s));
+    }
+    if (nullable) {
+        // slots 0 and 1 by the gather, slot 2 by the pack kernel, slot 3
+        // (seq) by a gather of its own
+        unsigned long long* d_bm = d_dst + size_t(n_cols) * n;
+        unsigned long long* d_nv = d_bm + bm_words;
+        unsigned long long* d_err = d_nv + nv_words;
+        HIP_TRY(hipMemsetAsync(d_err, 0, 8, s));
+        const unsigned long long* srcs[2] = {
+            (const unsigned long long*)rs.series,
+            (const unsigned long long*)rs.ts};
+        HIP_TRY(hx::launch_gather_multi(s, srcs, 2, perm, d_dst, n));
+        if (keep_seq)
+            HIP_TRY(hx::launch_gather_u64(
+                s, (const unsigned long long*)rs.seq, perm,
+                d_dst + 3 * size_t(n), n));
+        if (timed) HIP_TRY(hipEventRecord(ev[1], s));
+        HIP_TRY(hx::launch_pack_optional(
+            s, (const unsigned long long*)rs.val, rs.valid, false, perm, n, n,
+            (uint32_t)kRowGroup, d_dst + 2 * size_t(n), (uint64_t*)d_bm,
+            (uint32_t*)d_nv, d_err));
+    } else {
+        const unsigned long long* srcs[4] = {
+            (const unsigned long long*)rs.series,
+            (const unsigned long long*)rs.ts,
+            (const unsigned long long*)rs.val,
+            (const unsigned long long*)rs.seq};
+        HIP_TRY(hx::launch_gather_multi(s, srcs, n_cols, perm, d_dst, n));
+        if (timed) HIP_TRY(hipEventRecord(ev[1], s));
+    }
+    if (timed) HIP_TRY(hipEventRecord(ev[2], s));
+    // Writer codec Snappy: kernel 1e over the 8192-row slices of the columns
+    // where they sit in d_dst (series, ts, per-row seq, and value in its
+    // REQUIRED form; an OPTIONAL value page opens with its level block and
+    // goes through the host twin), then scan-and-pack and one D2H of the
+    // streams. Codec 0 launches nothing here.
+    DeviceStreams streams;
+    if (codec) {
+        const int64_t col_words[5] = {
+            0, (int64_t)n, nullable ? -1 : 2 * (int64_t)n,
+            keep_seq ? 3 * (int64_t)n : -1, -1};
+        HIP_TRY(compress_columns_device(s, (const uint8_t*)d_dst, col_words,
+                                        n, timed ? ev[3] : nullptr, streams));
+    } else if (timed) {
+        HIP_TRY(hipEventRecord(ev[3], s));
+    }
+    // what still has to come back raw: everything under codec 0; under
+    // Snappy only what kernel 1e did not take — the packed values and, behind
+    // the columns, the bitmaps, counts and error word of the nullable form
+    size_t raw_bytes = 0;
+    auto bring = [&](size_t w0, size_t w1) {
+        raw_bytes += (w1 - w0) * 8;
+        return hipMemcpyAsync(host.data() + w0, d_dst + w0, (w1 - w0) * 8,
+                              hipMemcpyDeviceToHost, s);
+    };
+    if (!codec) {
+        HIP_TRY(bring(0, words));
+    } else if (nullable) {
+        HIP_TRY(bring(2 * size_t(n), 3 * size_t(n)));
+        HIP_TRY(bring(size_t(n_cols) * n, words));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    dst_guard.reset();
+    if (timed) {
+        float gather_ms = 0, pack_ms = 0, comp_ms = 0;
+        HIP_TRY(hipEventElapsedTime(&gather_ms, ev[0], ev[1]));
+        HIP_TRY(hipEventElapsedTime(&pack_ms, ev[1], ev[2]));
+        HIP_TRY(hipEventElapsedTime(&comp_ms, ev[2], ev[3]));
+        fprintf(stderr,
+                "[hx] compact rows=%u cols_gathered=%u nullable=%d nulls=%d "
+                "codec=%d gather_ms=%.4f pack_ms=%.4f comp_ms=%.4f "
+                "d2h_bytes=%zu\n",
+                n, nullable ? n_cols - 1 : n_cols, int(nullable), int(nulls),
+                codec, gather_ms, pack_ms, comp_ms,
+                raw_bytes + streams.d2h_bytes);
+    }
+    const hx::PagePayload* ready =
+        streams.ready.empty() ? nullptr : streams.ready.data();
+
+    const NewSst out = next_sst(h);
+    // a column kernel 1e compressed never came to the host (null here): its
+    // pages and statistics are in `ready`
+    const uint64_t* h_series = streams.on_device[0] ? nullptr : host.data();
+    const int64_t* h_ts =
+        streams.on_device[1] ? nullptr : (const int64_t*)(host.data() + n);
+    const uint64_t* h_val =
+        streams.on_device[2] ? nullptr : host.data() + 2 * size_t(n);
+    const uint64_t* h_seq = keep_seq && !streams.on_device[3]
+                                ? host.data() + 3 * size_t(n) : nullptr;
+    std::string werr;
+    if (nullable) {
+        const uint64_t* h_bm = host.data() + size_t(n_cols) * n;
+        if (h_bm[bm_words + nv_words] != 0)
+            return fail(HX_ERR_HIP, "compact: sort permutation out of range");
+        hx::NullableValues nv{h_val, h_bm,
+                              (const uint32_t*)(h_bm + bm_words)};
+        werr = hx::write_metric_sst_nullable(out.path, h_series, h_ts, nv,
+                                             h_seq, out.seq, n, kRowGroup,
+                                             codec, ready);
+    } else if (keep_seq) {
+        werr = hx::write_metric_sst_seqs(out.path, h_series, h_ts,
+                                         (const double*)h_val, h_seq, n,
+                                         kRowGroup, codec, ready);
+    } else {
+        werr = hx::write_metric_sst(out.path, h_series, h_ts,
+                                    (const double*)h_val, out.seq, n,
+                                    kRowGroup, codec, ready);
+    }
+    if (!werr.empty()) return fail(HX_ERR_IO, werr);
+    return finish_compaction(h, out, in_set, out_new_seq);
+}
+
+// What hx_compact and hx_compact_files do with their input set: one scan
+// plan over whole files (like the executor) on the first device given, then
+// compact_rows.
+static hx_status prepare_and_compact(hx_handle* h,
+                                     const std::vector<char>& in_set,
+                                     bool keep_seq, const hx_device_set* devs,
+                                     uint64_t* out_new_seq) {
+    std::vector<hx_sst_desc> inputs;
+    for (size_t i = 0; i < h->ssts.size(); i++)
+        if (in_set[i])
+            inputs.push_back({h->ssts[i].path.c_str(), h->ssts[i].seq});
+    if (inputs.empty()) return HX_OK;
+    hx_scan_spec spec{};
+    spec.range = {INT64_MIN, INT64_MAX};
+    spec.ssts = inputs.data();
+    spec.n_ssts = inputs.size();
+    PreparedPtr P(nullptr, hx_prepared_free);
+    hx_status st = prepare_single(h, &spec, devs, P);
+    if (st != HX_OK) return st;
+    return compact_rows(h, P.get(), in_set, keep_seq, out_new_seq);
 }
 
 extern "C" hx_status hx_compact(hx_handle* h, hx_time_range range,
@@ -4351,28 +4262,7 @@ extern "C" hx_status hx_compact(hx_handle* h, hx_time_range range,
             }
         }
     }
-    std::vector<hx_sst_desc> inputs;
-    uint64_t max_seq = 0;
-    for (size_t i = 0; i < h->ssts.size(); i++) {
-        if (!in_set[i]) continue;
-        inputs.push_back({h->ssts[i].path.c_str(), h->ssts[i].seq});
-    }
-    for (const auto& s : h->ssts) max_seq = std::max(max_seq, s.seq);
-    if (inputs.size() < 1) return HX_OK;
-
-    hx_scan_spec spec{};
-    spec.range = {INT64_MIN, INT64_MAX};   // whole files, like the executor
-    spec.ssts = inputs.data();
-    spec.n_ssts = inputs.size();
-    int32_t dev0 = (devs && devs->device_ids && devs->n_devices > 0)
-                       ? devs->device_ids[0] : 0;
-    hx_device_set one{&dev0, 1};
-    hx_prepared* P = nullptr;
-    hx_status st = hx_prepare(h, &spec, &one, &P);
-    if (st != HX_OK) return st;
-    std::unique_ptr<hx_prepared, void (*)(hx_prepared*)> guard(
-        P, hx_prepared_free);
-    return compact_rows(h, P, in_set, max_seq, false, out_new_seq);
+    return prepare_and_compact(h, in_set, false, devs, out_new_seq);
 }
 
 extern "C" hx_status hx_compact_files(hx_handle* h,
@@ -4402,27 +4292,7 @@ extern "C" hx_status hx_compact_files(hx_handle* h,
                         "input seq not in catalog: " +
                             std::to_string(input_seqs[k]));
     }
-    std::vector<hx_sst_desc> inputs;
-    uint64_t max_seq = 0;
-    for (size_t i = 0; i < h->ssts.size(); i++) {
-        if (in_set[i]) inputs.push_back({h->ssts[i].path.c_str(),
-                                         h->ssts[i].seq});
-        max_seq = std::max(max_seq, h->ssts[i].seq);
-    }
-
-    hx_scan_spec spec{};
-    spec.range = {INT64_MIN, INT64_MAX};
-    spec.ssts = inputs.data();
-    spec.n_ssts = inputs.size();
-    int32_t dev0 = (devs && devs->device_ids && devs->n_devices > 0)
-                       ? devs->device_ids[0] : 0;
-    hx_device_set one{&dev0, 1};
-    hx_prepared* P = nullptr;
-    hx_status st = hx_prepare(h, &spec, &one, &P);
-    if (st != HX_OK) return st;
-    std::unique_ptr<hx_prepared, void (*)(hx_prepared*)> guard(
-        P, hx_prepared_free);
-    return compact_rows(h, P, in_set, max_seq, true, out_new_seq);
+    return prepare_and_compact(h, in_set, true, devs, out_new_seq);
 }
 
 // introspection used by CPU tests (no GPU needed): per-SST catalog entries
