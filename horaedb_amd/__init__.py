@@ -12,5 +12,7 @@ from .store import (  # noqa: F401
     AGG_MIN,
     AGG_MAX,
     AGG_AVG,
+    AGG_FIRST,
+    AGG_LAST,
     lib_path,
 )

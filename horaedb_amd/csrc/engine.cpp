@@ -36,6 +36,7 @@
 #include "stage_chunk.h"
 #include "def_levels.h"
 #include "ba_pages.h"
+#include "first_last.h"
 
 using hx::align64;
 using hx::ChunkRef;
@@ -1078,13 +1079,28 @@ struct HostTable {  // one device's sorted aggregate table, on host
     double* vmin = nullptr;
     double* vmax = nullptr;
     double* avg = nullptr;
+    // first/last (a TS pass): extreme timestamps and the bit
+    // patterns of the values there. When a value pass ran too, they live in
+    // the TS pass's own buffer (buf2), whose keys were checked against buf's.
+    int64_t* first_ts = nullptr;
+    uint64_t* first = nullptr;
+    int64_t* last_ts = nullptr;
+    uint64_t* last = nullptr;
+    void* buf2 = nullptr;
+    size_t cap2 = 0;
+    bool pinned2 = false;
     void release() {
         if (buf) {
             g_result_pool.release(buf, cap, pinned);
             buf = nullptr;
         }
+        if (buf2) {
+            g_result_pool.release(buf2, cap2, pinned2);
+            buf2 = nullptr;
+        }
         n = 0;
         cap = 0;
+        cap2 = 0;
     }
 };
 
@@ -1340,6 +1356,86 @@ static hx_status ensure_range(DevPlan& plan, const hx::AggParams& base,
     return HX_OK;
 }
 
+// Columns of a TS pass's contiguous SoA result (column c at d_dst + c * ng):
+// where its time extrema sit and where the resolved values go. -1: side not
+// asked.
+struct TsCols {
+    int32_t c_bucket = -1;
+    int32_t c_min = -1, c_max = -1;       // tmin / tmax, as the pass left them
+    int32_t c_first = -1, c_last = -1;    // value outputs behind the pass's own
+};
+
+// Host view of a TS pass's table: its min/max columns are the timestamps.
+static void set_ts_columns(HostTable& out, uint64_t* hb, size_t ng,
+                           const TsCols& c) {
+    out.vmin = out.vmax = nullptr;
+    out.first_ts = c.c_first >= 0 ? (int64_t*)(hb + size_t(c.c_min) * ng)
+                                  : nullptr;
+    out.first = c.c_first >= 0 ? hb + size_t(c.c_first) * ng : nullptr;
+    out.last_ts = c.c_last >= 0 ? (int64_t*)(hb + size_t(c.c_max) * ng)
+                                : nullptr;
+    out.last = c.c_last >= 0 ? hb + size_t(c.c_last) * ng : nullptr;
+}
+
+// On-device finish of a TS pass (kernel 3d), before the single
+// D2H: turn the pass's min/max columns into i64 timestamps in place, resolve
+// the values at those extrema under the same filter and dedup, and map the
+// value words to f64 bit patterns. Everything stays on plan.stream; the one
+// host read is the error word.
+static hx_status resolve_first_last(hx_prepared* P, DevPlan& plan,
+                                    int64_t bucket_ms,
+                                    unsigned long long* d_dst, size_t ng,
+                                    const TsCols& c, double* kernel_ms) {
+    hipStream_t s = plan.stream;
+    auto col = [&](int32_t i) {
+        return i >= 0 ? d_dst + size_t(i) * ng : nullptr;
+    };
+    if (c.c_min >= 0) HIP_TRY(hx::launch_map_words(s, col(c.c_min), ng, true));
+    if (c.c_max >= 0) HIP_TRY(hx::launch_map_words(s, col(c.c_max), ng, true));
+    if (c.c_first >= 0)
+        HIP_TRY(hipMemsetAsync(col(c.c_first), 0, ng * 8, s));
+    if (c.c_last >= 0) HIP_TRY(hipMemsetAsync(col(c.c_last), 0, ng * 8, s));
+    unsigned long long* d_err = plan.d_counters + 5;
+    HIP_TRY(hipMemsetAsync(d_err, 0, 8, s));
+    hx::AggParams A = base_params(P, plan);
+    A.bucket_ms = bucket_ms;
+    hx::ResolveParams Q{};
+    Q.gkey = (const uint64_t*)d_dst;
+    Q.gbucket = (const long long*)col(c.c_bucket);
+    Q.tmin = (const long long*)col(c.c_min);
+    Q.tmax = (const long long*)col(c.c_max);
+    Q.ofirst = col(c.c_first);
+    Q.olast = col(c.c_last);
+    Q.ng = (uint32_t)ng;
+    Q.err = d_err;
+    hipEvent_t e0 = plan.ev[0], e1 = plan.ev[1];
+    HIP_TRY(hipEventRecord(e0, s));
+    hipError_t ke = hx::launch_resolve_first_last(s, A, Q, plan.has_nulls);
+    if (ke != hipSuccess)
+        return fail(HX_ERR_HIP,
+                    std::string("first/last resolve launch failed: ") +
+                        hipGetErrorString(ke));
+    HIP_TRY(hipEventRecord(e1, s));
+    if (c.c_first >= 0)
+        HIP_TRY(hx::launch_map_words(s, col(c.c_first), ng, false));
+    if (c.c_last >= 0)
+        HIP_TRY(hx::launch_map_words(s, col(c.c_last), ng, false));
+    unsigned long long err = 0;
+    HIP_TRY(hipMemcpyAsync(&err, d_err, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+    if (getenv("HX_DEBUG"))
+        fprintf(stderr, "[hx] first/last resolve groups=%zu kernel_ms=%.2f "
+                        "unmatched_rows=%llu\n", ng, ms, err);
+    if (err)
+        return fail(HX_ERR_HIP, "first/last resolve: " + std::to_string(err) +
+                                    " surviving rows matched no group of "
+                                    "the time pass");
+    *kernel_ms += ms;
+    return HX_OK;
+}
+
 // Series-only grouping on the range path: the range kernel emits
 // each block's groups as one key-ordered run, two small kernels place the
 // runs in block order into the contiguous SoA result, and the host syncs
@@ -1352,7 +1448,10 @@ static hx_status exec_range_sorted(hx_prepared* P, DevPlan& plan,
                                    const hx_agg_spec* agg, uint32_t ops,
                                    HostTable& out, double* agg_kernel_ms,
                                    unsigned long long* matched_out,
-                                   bool* done) {
+                                   bool* done, uint32_t fl = 0) {
+    // fl != 0: the TS pass of a first/last request — ops is MIN and/or MAX
+    // over the rows' timestamps, and the values at those extrema are
+    // resolved on the device before the D2H
     hipStream_t s = plan.stream;
     const bool mm = (ops & (HX_AGG_MIN | HX_AGG_MAX)) != 0;
     const bool has_sum = (ops & (HX_AGG_SUM | HX_AGG_AVG)) != 0;
@@ -1366,8 +1465,13 @@ static hx_status exec_range_sorted(hx_prepared* P, DevPlan& plan,
     const int32_t c_min = has_min ? na++ : -1;
     const int32_t c_max = has_max ? na++ : -1;
     const int32_t c_avg = has_avg ? na++ : -1;
-    const uint32_t n_total = (uint32_t)na;
     const uint32_t n_stage = mm ? 5 : 3;
+    TsCols tc;
+    tc.c_min = c_min;
+    tc.c_max = c_max;
+    if (fl & HX_AGG_FIRST) tc.c_first = na++;
+    if (fl & HX_AGG_LAST) tc.c_last = na++;
+    const uint32_t n_cols = (uint32_t)na;   // the pass's own + resolved
 
     uint64_t staged = 0;
     for (const auto& sd : plan.ssts) staged += (uint64_t)sd.n_staged;
@@ -1391,7 +1495,7 @@ static hx_status exec_range_sorted(hx_prepared* P, DevPlan& plan,
         uint32_t ne = 1024;
         if (const char* e = getenv("HX_RANGE_NE"))
             ne = (uint32_t)strtoul(e, nullptr, 10);
-        const size_t need = size_t(cap) * 8 * (n_stage + n_total) +
+        const size_t need = size_t(cap) * 8 * (n_stage + n_cols) +
                             size_t(nb) * 12 + 256;
         hx_status st = ensure_dev(&plan.d_scratch, &plan.scratch_cap, need);
         if (st != HX_OK) return st;
@@ -1408,7 +1512,7 @@ static hx_status exec_range_sorted(hx_prepared* P, DevPlan& plan,
         O.vmin = mm ? (double*)carve8(cap) : nullptr;
         O.vmax = mm ? (double*)carve8(cap) : nullptr;
         unsigned long long* d_dst =
-            (unsigned long long*)carve8(size_t(cap) * n_total);
+            (unsigned long long*)carve8(size_t(cap) * n_cols);
         O.desc = (uint64_t*)carve8(nb);
         uint32_t* d_prefix = (uint32_t*)base;
         O.cap = cap;
@@ -1452,7 +1556,8 @@ static hx_status exec_range_sorted(hx_prepared* P, DevPlan& plan,
         hipEvent_t e0 = plan.ev[0], e1 = plan.ev[1];
         HIP_TRY(hipEventRecord(e0, s));
         hipError_t ke = hx::launch_scan_agg_range2(s, A, R, mm,
-                                                   plan.has_nulls, O);
+                                                   plan.has_nulls, O,
+                                                   fl != 0);
         if (ke != hipSuccess)
             return fail(HX_ERR_HIP,
                         std::string("range kernel launch failed: ") +
@@ -1500,7 +1605,12 @@ static hx_status exec_range_sorted(hx_prepared* P, DevPlan& plan,
         out.n = total;
         if (total == 0) return HX_OK;
         const size_t ng = (size_t)total;
-        const size_t bytes = ng * 8 * n_total;
+        if (fl) {
+            hx_status fs = resolve_first_last(P, plan, 0, d_dst, ng, tc,
+                                              agg_kernel_ms);
+            if (fs != HX_OK) return fs;
+        }
+        const size_t bytes = ng * 8 * n_cols;
         out.buf = g_result_pool.acquire(bytes, &out.pinned, &out.cap);
         if (!out.buf) return fail(HX_ERR_IO, "result alloc failed");
         HIP_TRY(hipMemcpyAsync(out.buf, d_dst, bytes, hipMemcpyDeviceToHost,
@@ -1515,6 +1625,7 @@ static hx_status exec_range_sorted(hx_prepared* P, DevPlan& plan,
         out.vmin = has_min ? (double*)(hb + size_t(c_min) * ng) : nullptr;
         out.vmax = has_max ? (double*)(hb + size_t(c_max) * ng) : nullptr;
         out.avg = has_avg ? (double*)(hb + size_t(c_avg) * ng) : nullptr;
+        if (fl) set_ts_columns(out, hb, ng, tc);
         return HX_OK;
     }
     plan.sorted_gave_up = true;
@@ -1575,7 +1686,9 @@ static hx_status exec_table(hx_prepared* P, DevPlan& plan,
                             const hx_agg_spec* agg, uint32_t ops,
                             BucketPlan bp, int32_t key_claim, HostTable& out,
                             double* agg_kernel_ms,
-                            unsigned long long* matched_out) {
+                            unsigned long long* matched_out,
+                            uint32_t fl = 0) {
+    // fl != 0: the TS pass of a first/last request, as in exec_range_sorted
     hipStream_t s = plan.stream;
     const bool bucket = agg->bucket_ms > 0;
     const bool mm = (ops & (HX_AGG_MIN | HX_AGG_MAX)) != 0;
@@ -1645,7 +1758,7 @@ static hx_status exec_table(hx_prepared* P, DevPlan& plan,
         if (est != HX_OK) return est;
         hipEvent_t e0 = plan.ev[0], e1 = plan.ev[1];
         HIP_TRY(hipEventRecord(e0, s));
-        HIP_TRY(hx::launch_scan_agg(s, A, 0, plan.has_nulls));
+        HIP_TRY(hx::launch_scan_agg(s, A, 0, plan.has_nulls, fl != 0));
         HIP_TRY(hipEventRecord(e1, s));
         HIP_TRY(hipStreamSynchronize(s));
         float ms = 0;
@@ -1698,9 +1811,12 @@ static hx_status exec_table(hx_prepared* P, DevPlan& plan,
     const uint32_t n_core = 1 + (bucket ? 1 : 0) + has_sum + has_cnt +
                             has_min + has_max;
     const uint32_t n_total = n_core + (has_avg ? 1 : 0);
-    // scratch: compact arrays (n_core) + sort keys in/out (2) + dst (n_total)
+    // resolved first/last value columns behind the pass's own (TS pass only)
+    const uint32_t n_cols = n_total + ((fl & HX_AGG_FIRST) ? 1 : 0) +
+                            ((fl & HX_AGG_LAST) ? 1 : 0);
+    // scratch: compact arrays (n_core) + sort keys in/out (2) + dst (n_cols)
     // + 3 perm arrays + counter
-    size_t need = size_t(n) * 8 * (n_core + 2 + n_total) +
+    size_t need = size_t(n) * 8 * (n_core + 2 + n_cols) +
                   size_t(n) * 4 * 3 + 256 + 2 * 2048 * 4;
     hx_status st = ensure_dev(&plan.d_scratch, &plan.scratch_cap, need);
     if (st != HX_OK) return st;
@@ -1718,7 +1834,7 @@ static hx_status exec_table(hx_prepared* P, DevPlan& plan,
     double* c_max = has_max ? (double*)carve8(n) : nullptr;
     uint64_t* keys_tmp = (uint64_t*)carve8(n);
     uint64_t* keys_out = (uint64_t*)carve8(n);
-    unsigned long long* d_dst = (unsigned long long*)carve8(size_t(n) * n_total);
+    unsigned long long* d_dst = (unsigned long long*)carve8(size_t(n) * n_cols);
     unsigned long long* d_nout = (unsigned long long*)carve8(1);
     uint32_t* compact_scratch = (uint32_t*)carve8(2048);  // 2x2048 u32
     uint32_t* perm_a = (uint32_t*)base; base += size_t(n) * 4;
@@ -1780,7 +1896,20 @@ static hx_status exec_table(hx_prepared* P, DevPlan& plan,
                                d_dst + size_t(off_cnt) * ng,
                                (double*)(d_dst + size_t(n_core) * ng), ng));
 
-    const size_t bytes = size_t(ng) * 8 * n_total;
+    TsCols tc;
+    if (fl) {
+        uint32_t nc = n_total;
+        tc.c_bucket = bucket ? (int32_t)off_bucket : -1;
+        tc.c_min = has_min ? (int32_t)off_min : -1;
+        tc.c_max = has_max ? (int32_t)off_max : -1;
+        if (fl & HX_AGG_FIRST) tc.c_first = (int32_t)nc++;
+        if (fl & HX_AGG_LAST) tc.c_last = (int32_t)nc++;
+        hx_status fs = resolve_first_last(P, plan, bucket ? agg->bucket_ms : 0,
+                                          d_dst, ng, tc, agg_kernel_ms);
+        if (fs != HX_OK) return fs;
+    }
+
+    const size_t bytes = size_t(ng) * 8 * n_cols;
     out.buf = g_result_pool.acquire(bytes, &out.pinned, &out.cap);
     if (!out.buf) return fail(HX_ERR_IO, "result alloc failed");
     HIP_TRY(hipMemcpyAsync(out.buf, d_dst, bytes, hipMemcpyDeviceToHost, s));
@@ -1793,34 +1922,23 @@ static hx_status exec_table(hx_prepared* P, DevPlan& plan,
     out.vmin = has_min ? (double*)(hb + off_min * ng) : nullptr;
     out.vmax = has_max ? (double*)(hb + off_max * ng) : nullptr;
     out.avg = has_avg ? (double*)(hb + size_t(n_core) * ng) : nullptr;
+    if (fl) set_ts_columns(out, hb, ng, tc);
     return HX_OK;
 }
 
-// Aggregate one device's plan into `out` (sorted by series[, bucket]). Two
-// routes: series-only grouping with a key-claim-safe sentinel takes the range
-// path (exec_range_sorted); everything else, and a range plan that gave up,
-// takes the global table (exec_table).
-hx_status exec_plan(hx_prepared* P, DevPlan& plan, const hx_agg_spec* agg,
-                    HostTable& out, double* agg_kernel_ms,
-                    unsigned long long* matched_out) {
-    if (P->h->bytes_value)
-        return fail(HX_ERR_UNSUPPORTED,
-                    "aggregates over Binary value columns are undefined "
-                    "(scan the rows with hx_scan instead)");
-    HIP_TRY(hipSetDevice(plan.device));
+// One aggregate pass over a decoded plan into `out` (sorted by series[,
+// bucket]). Two routes: series-only grouping with a key-claim-safe sentinel
+// takes the range path (exec_range_sorted); everything else, and a range plan
+// that gave up, takes the global table (exec_table). fl != 0: the TS pass of
+// a first/last request (agg->ops is then MIN and/or MAX, run over the rows'
+// timestamps); route selection, partition and table sizing are those of any
+// other pass.
+static hx_status exec_pass(hx_prepared* P, DevPlan& plan,
+                           const hx_agg_spec* agg, uint32_t fl, HostTable& out,
+                           double* agg_kernel_ms,
+                           unsigned long long* matched_out) {
     const uint32_t ops = kernel_ops(agg->ops);
     const bool bucket = agg->bucket_ms > 0;
-
-    hx_status sst_ = ensure_sset(P, plan);
-    if (sst_ != HX_OK) return sst_;
-
-    // decode results persist across exec calls on one prepared scan; for
-    // benchmarking encoded/compressed workloads HX_REDECODE=1 forces every
-    // step to repeat the decompress/decode stage (no cached decode output
-    // inside the timed region).
-    if (getenv("HX_REDECODE")) plan.decoded = false;
-    hx_status dst_ = ensure_decoded(plan, plan.stream);
-    if (dst_ != HX_OK) return dst_;
 
     // one-CAS key claim: series-only grouping, or direct-indexed buckets,
     // with a stats-proven sentinel (HX_FORCE_STATE=1 forces the generic
@@ -1849,11 +1967,82 @@ hx_status exec_plan(hx_prepared* P, DevPlan& plan, const hx_agg_spec* agg,
     if (use_range && plan.range_ready) {
         bool done = false;
         hx_status rs = exec_range_sorted(P, plan, agg, ops, out,
-                                         agg_kernel_ms, matched_out, &done);
+                                         agg_kernel_ms, matched_out, &done,
+                                         fl);
         if (rs != HX_OK || done) return rs;
     }
     return exec_table(P, plan, agg, ops, bp, key_claim, out, agg_kernel_ms,
-                      matched_out);
+                      matched_out, fl);
+}
+
+// Aggregate one device's plan into `out`. The request splits into the value
+// ops (sum, count, min, max, avg: one pass, as before first/last existed) and
+// first/last (a TS pass plus the on-device resolve). Both passes
+// skip the same rows, so they must agree on the group set and on the matched
+// row count; that is checked, never assumed.
+hx_status exec_plan(hx_prepared* P, DevPlan& plan, const hx_agg_spec* agg,
+                    HostTable& out, double* agg_kernel_ms,
+                    unsigned long long* matched_out) {
+    if (P->h->bytes_value)
+        return fail(HX_ERR_UNSUPPORTED,
+                    "aggregates over Binary value columns are undefined "
+                    "(scan the rows with hx_scan instead)");
+    HIP_TRY(hipSetDevice(plan.device));
+
+    hx_status sst_ = ensure_sset(P, plan);
+    if (sst_ != HX_OK) return sst_;
+
+    // decode results persist across exec calls on one prepared scan; for
+    // benchmarking encoded/compressed workloads HX_REDECODE=1 forces every
+    // step to repeat the decompress/decode stage (no cached decode output
+    // inside the timed region). Once per exec, not once per pass.
+    if (getenv("HX_REDECODE")) plan.decoded = false;
+    hx_status dst_ = ensure_decoded(plan, plan.stream);
+    if (dst_ != HX_OK) return dst_;
+
+    const uint32_t fl = agg->ops & (HX_AGG_FIRST | HX_AGG_LAST);
+    const uint32_t vops = agg->ops & ~fl;
+    if (!fl)
+        return exec_pass(P, plan, agg, 0, out, agg_kernel_ms, matched_out);
+    const hx_agg_spec tspec{((fl & HX_AGG_FIRST) ? (uint32_t)HX_AGG_MIN : 0u) |
+                                ((fl & HX_AGG_LAST) ? (uint32_t)HX_AGG_MAX : 0u),
+                            agg->bucket_ms};
+    if (!vops)
+        return exec_pass(P, plan, &tspec, fl, out, agg_kernel_ms, matched_out);
+
+    const hx_agg_spec vspec{vops, agg->bucket_ms};
+    hx_status st = exec_pass(P, plan, &vspec, 0, out, agg_kernel_ms,
+                             matched_out);
+    if (st != HX_OK) return st;
+    HostTable ts;
+    double ts_ms = 0;
+    unsigned long long ts_matched = 0;
+    st = exec_pass(P, plan, &tspec, fl, ts, &ts_ms, &ts_matched);
+    if (st == HX_OK && ts_matched != *matched_out)
+        st = fail(HX_ERR_HIP, "first/last: the time pass matched " +
+                                  std::to_string(ts_matched) +
+                                  " rows, the value pass " +
+                                  std::to_string(*matched_out));
+    if (st == HX_OK &&
+        (ts.n != out.n ||
+         (ts.n && memcmp(ts.series, out.series, ts.n * 8) != 0) ||
+         (ts.n && agg->bucket_ms > 0 &&
+          memcmp(ts.bucket, out.bucket, ts.n * 8) != 0)))
+        st = fail(HX_ERR_HIP, "first/last: the time pass and the value pass "
+                              "disagree on the group set");
+    if (st != HX_OK) {
+        ts.release();
+        return st;
+    }
+    *agg_kernel_ms += ts_ms;
+    out.first_ts = ts.first_ts;
+    out.first = ts.first;
+    out.last_ts = ts.last_ts;
+    out.last = ts.last;
+    out.buf2 = ts.buf;   // ownership moves with the columns
+    out.cap2 = ts.cap;
+    out.pinned2 = ts.pinned;
+    return HX_OK;
 }
 
 }  // namespace
@@ -1869,6 +2058,8 @@ struct ResultStorage {  // backs hx_result_table arrays
     std::vector<double> sum;
     std::vector<unsigned long long> cnt;
     std::vector<double> vmin, vmax, avg;
+    std::vector<int64_t> first_ts, last_ts;
+    std::vector<uint64_t> first, last;   // f64 bit patterns
 };
 
 // n-way merge of per-device sorted partials, combining equal (series,bucket)
@@ -1892,6 +2083,7 @@ void merge_partials(std::vector<HostTable>& parts, uint32_t ops,
         if (!any) break;
         double sum = 0, vmin = 0, vmax = 0;
         unsigned long long cnt = 0;
+        hx::FlPick pf{0, 0}, pl{0, 0};   // first_last.h states the rules
         bool first = true;
         for (size_t p = 0; p < parts.size(); p++) {
             size_t i = idx[p];
@@ -1904,6 +2096,14 @@ void merge_partials(std::vector<HostTable>& parts, uint32_t ops,
                 vmin = first ? parts[p].vmin[i] : std::min(vmin, parts[p].vmin[i]);
             if (kops & HX_AGG_MAX)
                 vmax = first ? parts[p].vmax[i] : std::max(vmax, parts[p].vmax[i]);
+            if (ops & HX_AGG_FIRST) {
+                const hx::FlPick x{parts[p].first_ts[i], parts[p].first[i]};
+                pf = first ? x : hx::fl_merge_first(pf, x);
+            }
+            if (ops & HX_AGG_LAST) {
+                const hx::FlPick x{parts[p].last_ts[i], parts[p].last[i]};
+                pl = first ? x : hx::fl_merge_last(pl, x);
+            }
             first = false;
             idx[p]++;
         }
@@ -1914,6 +2114,14 @@ void merge_partials(std::vector<HostTable>& parts, uint32_t ops,
         if (ops & HX_AGG_MIN) out.vmin.push_back(vmin);
         if (ops & HX_AGG_MAX) out.vmax.push_back(vmax);
         if (ops & HX_AGG_AVG) out.avg.push_back(sum / double(cnt));
+        if (ops & HX_AGG_FIRST) {
+            out.first_ts.push_back(pf.ts);
+            out.first.push_back(pf.bits);
+        }
+        if (ops & HX_AGG_LAST) {
+            out.last_ts.push_back(pl.ts);
+            out.last.push_back(pl.bits);
+        }
     }
 }
 
@@ -1952,6 +2160,7 @@ extern "C" hx_status hx_exec_agg(hx_prepared* P, const hx_agg_spec* agg,
     if (parts.size() == 1) {
         R->owned = parts[0];
         parts[0].buf = nullptr;  // ownership moved
+        parts[0].buf2 = nullptr;
         const HostTable& H = R->owned;
         T.n_groups = H.n;
         T.series_id = H.series;
@@ -1961,6 +2170,14 @@ extern "C" hx_status hx_exec_agg(hx_prepared* P, const hx_agg_spec* agg,
         T.vmin = (agg->ops & HX_AGG_MIN) ? H.vmin : nullptr;
         T.vmax = (agg->ops & HX_AGG_MAX) ? H.vmax : nullptr;
         T.avg = (agg->ops & HX_AGG_AVG) ? H.avg : nullptr;
+        if (agg->ops & HX_AGG_FIRST) {
+            T.first = (const double*)H.first;
+            T.first_ts = H.first_ts;
+        }
+        if (agg->ops & HX_AGG_LAST) {
+            T.last = (const double*)H.last;
+            T.last_ts = H.last_ts;
+        }
     } else {
         merge_partials(parts, agg->ops, bucket, R->store);
         for (auto& p : parts) p.release();
@@ -1972,6 +2189,14 @@ extern "C" hx_status hx_exec_agg(hx_prepared* P, const hx_agg_spec* agg,
         T.vmin = (agg->ops & HX_AGG_MIN) ? R->store.vmin.data() : nullptr;
         T.vmax = (agg->ops & HX_AGG_MAX) ? R->store.vmax.data() : nullptr;
         T.avg = (agg->ops & HX_AGG_AVG) ? R->store.avg.data() : nullptr;
+        if (agg->ops & HX_AGG_FIRST) {
+            T.first = (const double*)R->store.first.data();
+            T.first_ts = R->store.first_ts.data();
+        }
+        if (agg->ops & HX_AGG_LAST) {
+            T.last = (const double*)R->store.last.data();
+            T.last_ts = R->store.last_ts.data();
+        }
     }
 
     P->last_stats.exec_ms = std::chrono::duration<double, std::milli>(

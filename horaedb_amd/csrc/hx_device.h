@@ -173,6 +173,21 @@ struct RangePlace {
     const unsigned long long* block_ovf;
 };
 
+// First/last resolve (k_resolve_first_last, DESIGN §4 kernel 3d): the sorted
+// groups of the TS pass with their time extrema; a side that was not asked
+// has null tmin/ofirst (tmax/olast). Outputs are f64_ordered words,
+// zero-filled by the caller.
+struct ResolveParams {
+    const uint64_t* gkey;          // ng series ids, sorted by (series, bucket)
+    const long long* gbucket;      // ng bucket indices, null: series-only
+    const long long* tmin;         // ng smallest surviving non-null ts
+    const long long* tmax;         // ng greatest
+    unsigned long long* ofirst;    // ng
+    unsigned long long* olast;     // ng
+    uint32_t ng;
+    unsigned long long* err;       // rows that found no group (must stay 0)
+};
+
 // DELTA_BINARY_PACKED decode unit: one page -> dense i64 at dst_off (dec).
 struct DeltaPageDesc {
     uint64_t src_off;     // page payload (bit63: in dec blob, e.g. post-snappy)

@@ -75,9 +75,11 @@ hipError_t launch_page_minmax(hipStream_t s, const uint8_t* src,
                               PageStat* out);
 hipError_t launch_copy_u64(hipStream_t s, const uint8_t* blob, uint8_t* dec,
                            const CopyDesc* descs, uint32_t n_descs);
-// nulls: the plan staged a validity bitmap — launch the null-aware instance
+// nulls: the plan staged a validity bitmap — launch the null-aware instance.
+// ts: the TS instance (first/last): min/max run over the rows'
+// timestamps instead of their values; p.ops must ask for MIN or MAX.
 hipError_t launch_scan_agg(hipStream_t s, const AggParams& p, uint32_t grid,
-                           bool nulls = false);
+                           bool nulls = false, bool ts = false);
 // Series-range mode: sample series for quantile boundaries,
 // precompute per-(block,sst) row bounds, then the LDS-table range kernel
 // (k_scan_agg_range2; the name is kept so the profiles/ records match).
@@ -90,10 +92,19 @@ hipError_t launch_range_bounds(hipStream_t s, const AggParams& p,
 // not used); launch_place_runs then assembles the result.
 hipError_t launch_scan_agg_range2(hipStream_t s, const AggParams& p,
                                   const RangeAux& r, bool minmax,
-                                  bool nulls, const RangeOut& out);
+                                  bool nulls, const RangeOut& out,
+                                  bool ts = false);
 // Exclusive scan of the run counts in blk order, then one copy of every run
 // to its final position in the contiguous SoA result (avg computed here).
 hipError_t launch_place_runs(hipStream_t s, const RangePlace& q);
+// Kernel 3d: p carries the filter, dedup and bucket_ms of the aggregate; the
+// caller zero-fills q.ofirst / q.olast on the same stream first.
+hipError_t launch_resolve_first_last(hipStream_t s, const AggParams& p,
+                                     const ResolveParams& q, bool nulls);
+// In place, n words. to_ts: min/max columns of a TS pass (written through
+// ordered_f64) -> i64 timestamps; else ordered value words -> f64 bits.
+hipError_t launch_map_words(hipStream_t s, unsigned long long* w, size_t n,
+                            bool to_ts);
 hipError_t launch_scan_rows(hipStream_t s, const AggParams& p,
                             uint32_t rg_first, uint32_t rg_last,
                             uint64_t* out_series, long long* out_ts,

@@ -48,6 +48,12 @@ __device__ __forceinline__ double ordered_f64(unsigned long long u) {
     return __longlong_as_double((u >> 63) ? (u & 0x7FFFFFFFFFFFFFFFull) : ~u);
 }
 
+// order-preserving i64 -> u64 map of a timestamp, full range: the TS
+// instances of the aggregate kernels run their min/max machinery on it
+__device__ __forceinline__ unsigned long long ts_ordered(int64_t t) {
+    return (unsigned long long)t ^ 0x8000000000000000ull;
+}
+
 __device__ __forceinline__ int64_t floordiv(int64_t a, int64_t b) {
     int64_t q = a / b;
     if ((a % b) != 0 && ((a < 0) != (b < 0))) q--;
@@ -363,7 +369,7 @@ struct WinResult {
     uint64_t hint_k;    // its key value at probe time
 };
 
-template <bool NULLS, bool MM>
+template <bool NULLS, bool MM, bool TS>
 __device__ __forceinline__ void scan_window(const AggParams& P,
                                             const RgDesc& rg, uint32_t rgi,
                                             const SstDev& sst,
@@ -425,7 +431,9 @@ __device__ __forceinline__ void scan_window(const AggParams& P,
     // ordered words with the ordered identities: a dead lane must lose to
     // every live value, +NaN in a min and -NaN in a max included. Only the
     // MM instances (min or max requested) carry them through the reduction.
-    const unsigned long long ov = f64_ordered(v);
+    // The TS instances (first/last) feed the same reduction the
+    // row's timestamp as an ordered word in place of the value's.
+    const unsigned long long ov = TS ? ts_ordered(t) : f64_ordered(v);
     unsigned long long mn = (MM && alive) ? ov : ~0ull;
     unsigned long long mx = (MM && alive) ? ov : 0ull;
     if (!NULLS) my_matched += c;
@@ -477,7 +485,7 @@ __device__ __forceinline__ void scan_window(const AggParams& P,
 // dependent table-update chains (L3 probe + atomics) overlap — the kernel
 // is memory-latency-bound (SQ_WAIT_ANY 76%) at full occupancy, so the
 // lever is per-wave memory-level parallelism.
-template <bool NULLS, bool MM>
+template <bool NULLS, bool MM, bool TS>
 __global__ void __launch_bounds__(256)
 k_scan_agg(AggParams P) {
     unsigned long long my_matched = 0;
@@ -511,11 +519,11 @@ k_scan_agg(AggParams P) {
             WinResult A, B;
             B.c = 0;
             B.head = false;
-            scan_window<NULLS, MM>(P, rg, rgi, sst, S, T, V, base, n, lane,
+            scan_window<NULLS, MM, TS>(P, rg, rgi, sst, S, T, V, base, n, lane,
                                    my_matched, A);
             const uint32_t base2 = base + blockDim.x;
             if (base2 < n)
-                scan_window<NULLS, MM>(P, rg, rgi, sst, S, T, V, base2, n,
+                scan_window<NULLS, MM, TS>(P, rg, rgi, sst, S, T, V, base2, n,
                                        lane, my_matched, B);
             const bool upA = A.head && A.c > 0;
             const bool upB = B.head && B.c > 0;
@@ -764,7 +772,7 @@ __device__ __forceinline__ void emit_sorted_run(
     }
 }
 
-template <bool MM, bool NULLS>
+template <bool MM, bool NULLS, bool TS>
 __global__ void __launch_bounds__(256)
 k_scan_agg_range2(AggParams P, RangeAux R, RangeOut O) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -929,21 +937,25 @@ k_scan_agg_range2(AggParams P, RangeAux R, RangeOut O) {
                     // others compute none of this)
                     const bool merge = a0 && a1 && (s0 == s1);
                     if (merge) {
-                        const unsigned long long o0 = f64_ordered(v0);
-                        const unsigned long long o1 = f64_ordered(v1);
+                        const unsigned long long o0 =
+                            TS ? ts_ordered(t0) : f64_ordered(v0);
+                        const unsigned long long o1 =
+                            TS ? ts_ordered(t1) : f64_ordered(v1);
                         const bool lt = o1 < o0;
                         lost |= !lds_update<MM>(
                             lkey, lsum, lcnt, lmin, lmax, ne, s0, v0 + v1,
                             2u, lt ? o1 : o0, lt ? o0 : o1, iA, preA);
                     } else {
                         if (a0) {
-                            const unsigned long long o = f64_ordered(v0);
+                            const unsigned long long o =
+                                TS ? ts_ordered(t0) : f64_ordered(v0);
                             lost |= !lds_update<MM>(
                                 lkey, lsum, lcnt, lmin, lmax, ne, s0, v0,
                                 1u, o, o, iA, preA);
                         }
                         if (a1) {
-                            const unsigned long long o = f64_ordered(v1);
+                            const unsigned long long o =
+                                TS ? ts_ordered(t1) : f64_ordered(v1);
                             lost |= !lds_update<MM>(
                                 lkey, lsum, lcnt, lmin, lmax, ne, s1, v1,
                                 1u, o, o, iB, preB);
@@ -1038,6 +1050,128 @@ k_place_runs(RangePlace Q) {
             if (d_max) d_max[o] = Q.vmax[i];
             if (d_avg) d_avg[o] = sm / (double)c;
         }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Kernel 3d, first/last resolve. The TS pass left, per group, the
+// smallest and greatest timestamp of its surviving non-null rows. This kernel
+// walks the rows once more under the same filter and dedup (row_alive,
+// row_valid, hx_ptr) and, for every such row whose timestamp IS its group's
+// extreme, atomicMax-es the value's ordered word into the group's output
+// word: on a well-formed store one row per group and side gets there, and
+// when two tie (the same PK surviving in two time segments) the
+// totalOrder-greater value wins whatever the row order. Outputs are
+// zero-filled by the host (the ordered identity of max).
+// Group lookup: rows of a slice ascend by (series, ts), so by (series,
+// bucket). Per 64-row window two wave-cooperative 64-ary lower bounds over
+// the sorted group keys (first and last row of the window) bracket the
+// window's groups; each lane finishes with a binary search inside the
+// bracket. A row that finds no group is counted in Q.err and skipped.
+// Reads: the slices' columns and bitmaps, [0, ng) of the group arrays.
+// Writes: ofirst/olast[0, ng) and the error counter.
+// ---------------------------------------------------------------------------
+template <typename Less>
+__device__ __forceinline__ uint32_t lb64_if(uint32_t n, int lane,
+                                            Less lt_target) {
+    uint32_t lo = 0, rem = n;
+    while (rem > 0) {
+        const uint32_t step = (rem + 63u) >> 6;
+        const uint32_t p = lo + (uint32_t)lane * step;
+        const bool in = (uint32_t)lane * step < rem;
+        const bool t = in && lt_target(p);
+        const uint32_t k = (uint32_t)__popcll(__ballot(t));
+        if (k == 0) break;
+        const uint32_t adv = (k - 1) * step + 1;
+        lo += adv;
+        rem = (step - 1u) < (rem - adv) ? (step - 1u) : (rem - adv);
+    }
+    return lo;   // first index whose key is not below the target (n if none)
+}
+
+template <bool NULLS>
+__global__ void __launch_bounds__(256)
+k_resolve_first_last(AggParams P, ResolveParams Q) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t wave = threadIdx.x >> 6;
+    const uint32_t n_waves = blockDim.x >> 6;
+    const uint32_t ng = Q.ng;
+    // group g's key < (s, b)?  g < ng at every call
+    auto key_lt = [&](uint32_t g, uint64_t s, int64_t b) {
+        const uint64_t ks = Q.gkey[g];
+        if (ks != s) return ks < s;
+        return Q.gbucket ? (Q.gbucket[g] < b) : false;
+    };
+    unsigned long long bad = 0;
+    for (uint32_t rgi = blockIdx.x; rgi < P.n_rgs; rgi += gridDim.x) {
+        const RgDesc rg = P.rgs[rgi];
+        const uint64_t* S = (const uint64_t*)hx_ptr(P.blob, P.dec, rg.series_off);
+        const int64_t* T = (const int64_t*)hx_ptr(P.blob, P.dec, rg.ts_off);
+        const double* V = (const double*)hx_ptr(P.blob, P.dec, rg.val_off);
+        const SstDev sst = P.ssts[rg.sst_id];
+        const uint32_t n = rg.n_rows;
+        for (uint32_t base = wave * 64u; base < n; base += n_waves * 64u) {
+            const uint32_t r = base + (uint32_t)lane;
+            const bool inb = r < n;
+            uint64_t s = 0;
+            int64_t t = 0;
+            double v = 0.0;
+            if (inb) {
+                s = S[r];
+                t = T[r];
+                v = V[r];
+            }
+            bool alive = inb && row_alive(P, rg, sst, S, T, r, n, s, t);
+            if (NULLS && alive) alive = row_valid(P, rgi, r);
+            if (!__any(alive)) continue;   // wave-uniform
+            const int64_t b = P.bucket_ms ? floordiv(t, P.bucket_ms) : 0;
+            // bracket: the keys of the window's first and last row (alive or
+            // not, they bound every row between them)
+            const int last = (int)((n - base < 64u ? n - base : 64u) - 1u);
+            const uint64_t sF = __shfl(s, 0, 64);
+            const int64_t bF = __shfl((long long)b, 0, 64);
+            const uint64_t sL = __shfl(s, last, 64);
+            const int64_t bL = __shfl((long long)b, last, 64);
+            const uint32_t g0 = lb64_if(
+                ng, lane, [&](uint32_t p) { return key_lt(p, sF, bF); });
+            const uint32_t g1 = lb64_if(
+                ng, lane, [&](uint32_t p) { return key_lt(p, sL, bL); });
+            if (!alive) continue;
+            uint32_t lo = g0 < ng ? g0 : ng;
+            uint32_t hi = g1 < ng ? g1 + 1u : ng;   // search [lo, hi)
+            while (lo < hi) {
+                const uint32_t mid = lo + ((hi - lo) >> 1);
+                if (key_lt(mid, s, b)) lo = mid + 1u;
+                else hi = mid;
+            }
+            const bool found = lo < ng && Q.gkey[lo] == s &&
+                               (!Q.gbucket || Q.gbucket[lo] == b);
+            if (!found) {   // the TS pass saw every row this pass sees
+                bad++;
+                continue;
+            }
+            const unsigned long long o = f64_ordered(v);
+            if (Q.olast && t == Q.tmax[lo]) atomicMax(&Q.olast[lo], o);
+            if (Q.ofirst && t == Q.tmin[lo]) atomicMax(&Q.ofirst[lo], o);
+        }
+    }
+    if (bad) __hip_atomic_fetch_add(Q.err, bad, RLX, AGT);
+}
+
+// In-place word maps around kernel 3d. to_ts: a column the aggregate emit
+// paths wrote through ordered_f64 holds the image of a time word; f64_ordered
+// inverts that bijection exactly and the sign flip gives the i64 timestamp.
+// Otherwise: ordered value words -> the f64 bit patterns they stand for.
+// No floating-point arithmetic touches either.
+extern "C" __global__ void __launch_bounds__(256)
+k_map_words(unsigned long long* w, size_t n, uint32_t to_ts) {
+    for (size_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n;
+         i += (size_t)blockDim.x * gridDim.x) {
+        const unsigned long long u = w[i];
+        w[i] = to_ts
+            ? (f64_ordered(__longlong_as_double((long long)u)) ^
+               0x8000000000000000ull)
+            : (unsigned long long)__double_as_longlong(ordered_f64(u));
     }
 }
 
@@ -3678,25 +3812,33 @@ hipError_t launch_copy_u64(hipStream_t s, const uint8_t* blob, uint8_t* dec,
 }
 
 hipError_t launch_scan_agg(hipStream_t s, const AggParams& p, uint32_t grid,
-                           bool nulls) {
+                           bool nulls, bool ts) {
     if (grid == 0) grid = p.n_rgs > 65535 ? 65535 : (p.n_rgs ? p.n_rgs : 1);
     // NULLS is a launch-level template parameter, as for the range kernel:
     // a wrapper around one shared body costs the null-off instance 3 VGPRs.
     // MM likewise: the ordered-word min/max reduction is compiled into the
     // instances a min/max query launches and into no other.
     const bool mm = (p.ops & (HXK_MIN | HXK_MAX)) != 0;
-    if (nulls && mm)
-        hipLaunchKernelGGL((k_scan_agg<true, true>), dim3(grid), dim3(256),
-                           0, s, p);
+    if (ts) {   // TS implies MM: the time words ride the min/max slots
+        if (!mm) return hipErrorInvalidValue;
+        if (nulls)
+            hipLaunchKernelGGL((k_scan_agg<true, true, true>), dim3(grid),
+                               dim3(256), 0, s, p);
+        else
+            hipLaunchKernelGGL((k_scan_agg<false, true, true>), dim3(grid),
+                               dim3(256), 0, s, p);
+    } else if (nulls && mm)
+        hipLaunchKernelGGL((k_scan_agg<true, true, false>), dim3(grid),
+                           dim3(256), 0, s, p);
     else if (nulls)
-        hipLaunchKernelGGL((k_scan_agg<true, false>), dim3(grid), dim3(256),
-                           0, s, p);
+        hipLaunchKernelGGL((k_scan_agg<true, false, false>), dim3(grid),
+                           dim3(256), 0, s, p);
     else if (mm)
-        hipLaunchKernelGGL((k_scan_agg<false, true>), dim3(grid), dim3(256),
-                           0, s, p);
+        hipLaunchKernelGGL((k_scan_agg<false, true, false>), dim3(grid),
+                           dim3(256), 0, s, p);
     else
-        hipLaunchKernelGGL((k_scan_agg<false, false>), dim3(grid), dim3(256),
-                           0, s, p);
+        hipLaunchKernelGGL((k_scan_agg<false, false, false>), dim3(grid),
+                           dim3(256), 0, s, p);
     return hipGetLastError();
 }
 
@@ -3722,33 +3864,39 @@ hipError_t launch_range_bounds(hipStream_t s, const AggParams& p,
     return hipGetLastError();
 }
 
-template <bool MM, bool NULLS>
+template <bool MM, bool NULLS, bool TS>
 static hipError_t launch_range2_inst(hipStream_t s, const AggParams& p,
                                      const RangeAux& r, const RangeOut& o) {
     // per slot: key 8 + sum 8 + cnt 4 [+ min 8 + max 8] + sort index 2
     const size_t lds = (size_t)r.ne * (MM ? 38 : 22);
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(
-            reinterpret_cast<const void*>(&k_scan_agg_range2<MM, NULLS>),
+            reinterpret_cast<const void*>(&k_scan_agg_range2<MM, NULLS, TS>),
             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((k_scan_agg_range2<MM, NULLS>), dim3(r.n_blocks),
+    hipLaunchKernelGGL((k_scan_agg_range2<MM, NULLS, TS>), dim3(r.n_blocks),
                        dim3(256), lds, s, p, r, o);
     return hipGetLastError();
 }
 
 hipError_t launch_scan_agg_range2(hipStream_t s, const AggParams& p,
                                   const RangeAux& r, bool minmax,
-                                  bool nulls, const RangeOut& out) {
+                                  bool nulls, const RangeOut& out,
+                                  bool ts) {
     // the sort permutation is u16 and the slot mask needs a power of two
     if (r.ne == 0 || (r.ne & (r.ne - 1)) || r.ne > 32768u)
         return hipErrorInvalidValue;
+    if (ts) {   // TS implies MM
+        if (!minmax) return hipErrorInvalidValue;
+        return nulls ? launch_range2_inst<true, true, true>(s, p, r, out)
+                     : launch_range2_inst<true, false, true>(s, p, r, out);
+    }
     if (nulls)
-        return minmax ? launch_range2_inst<true, true>(s, p, r, out)
-                      : launch_range2_inst<false, true>(s, p, r, out);
-    return minmax ? launch_range2_inst<true, false>(s, p, r, out)
-                  : launch_range2_inst<false, false>(s, p, r, out);
+        return minmax ? launch_range2_inst<true, true, false>(s, p, r, out)
+                      : launch_range2_inst<false, true, false>(s, p, r, out);
+    return minmax ? launch_range2_inst<true, false, false>(s, p, r, out)
+                  : launch_range2_inst<false, false, false>(s, p, r, out);
 }
 
 hipError_t launch_place_runs(hipStream_t s, const RangePlace& q) {
@@ -3758,6 +3906,31 @@ hipError_t launch_place_runs(hipStream_t s, const RangePlace& q) {
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_place_runs, dim3(grid_for(q.n_blocks, 4)), dim3(256),
                        0, s, q);
+    return hipGetLastError();
+}
+
+hipError_t launch_resolve_first_last(hipStream_t s, const AggParams& p,
+                                     const ResolveParams& q, bool nulls) {
+    if (q.ng == 0 || !q.gkey || !q.err || (!q.ofirst && !q.olast) ||
+        (q.ofirst && !q.tmin) || (q.olast && !q.tmax))
+        return hipErrorInvalidValue;
+    const uint32_t grid = p.n_rgs > 65535 ? 65535 : (p.n_rgs ? p.n_rgs : 1);
+    if (nulls)
+        hipLaunchKernelGGL((k_resolve_first_last<true>), dim3(grid),
+                           dim3(256), 0, s, p, q);
+    else
+        hipLaunchKernelGGL((k_resolve_first_last<false>), dim3(grid),
+                           dim3(256), 0, s, p, q);
+    return hipGetLastError();
+}
+
+hipError_t launch_map_words(hipStream_t s, unsigned long long* w, size_t n,
+                            bool to_ts) {
+    if (n == 0) return hipSuccess;
+    size_t blocks = (n + 255) / 256;
+    if (blocks > 65535) blocks = 65535;
+    hipLaunchKernelGGL(k_map_words, dim3((uint32_t)blocks), dim3(256), 0, s,
+                       w, n, to_ts ? 1u : 0u);
     return hipGetLastError();
 }
 

@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.join(_HERE, "libhoraedb_hx.so")
 
 AGG_SUM, AGG_COUNT, AGG_MIN, AGG_MAX, AGG_AVG = 1, 2, 4, 8, 16
+AGG_FIRST, AGG_LAST = 32, 64
 
 _ERRNAMES = {0: "OK", 1: "IO", 2: "FORMAT", 3: "UNSUPPORTED", 4: "NO_GPU",
              5: "HIP", 6: "INVALID", 7: "SCHEMA"}
@@ -58,7 +59,11 @@ class _ResultTable(C.Structure):
                 ("count", C.POINTER(C.c_uint64)),
                 ("vmin", C.POINTER(C.c_double)),
                 ("vmax", C.POINTER(C.c_double)),
-                ("avg", C.POINTER(C.c_double))]
+                ("avg", C.POINTER(C.c_double)),
+                ("first", C.POINTER(C.c_double)),
+                ("first_ts", C.POINTER(C.c_int64)),
+                ("last", C.POINTER(C.c_double)),
+                ("last_ts", C.POINTER(C.c_int64))]
 
 
 class _ColBatch(C.Structure):
@@ -234,6 +239,19 @@ class HeldResult:
             res["vmax"] = col(t.vmax, np.float64)
         if ops & AGG_AVG:
             res["avg"] = col(t.avg, np.float64)
+
+        def bits_col(ptr):
+            # the value columns of first/last travel as 64-bit words, so the
+            # float64 arrays carry the stored bits (NaN payloads included)
+            return col(C.cast(ptr, C.POINTER(C.c_uint64)),
+                       np.uint64).view(np.float64)
+
+        if ops & AGG_FIRST:
+            res["first"] = bits_col(t.first)
+            res["first_ts"] = col(t.first_ts, np.int64)
+        if ops & AGG_LAST:
+            res["last"] = bits_col(t.last)
+            res["last_ts"] = col(t.last_ts, np.int64)
         return res
 
     def close(self):

@@ -98,6 +98,8 @@ enum {
     HX_AGG_MIN   = 1u << 2,
     HX_AGG_MAX   = 1u << 3,
     HX_AGG_AVG   = 1u << 4,   /* finalized as sum/count */
+    HX_AGG_FIRST = 1u << 5,   /* value at the group's smallest timestamp */
+    HX_AGG_LAST  = 1u << 6,   /* value at the group's greatest timestamp */
 };
 /* Null values (OPTIONAL f64 value column): a row with a null value is still
  * a row — it passes or fails the filter and takes part in dedup like any
@@ -138,7 +140,34 @@ enum {
  *              come back unchanged. Files written here carry DOUBLE
  *              statistics as parquet-format demands: no NaN in min/max (a
  *              row group of nothing but NaN carries none), a zero bound
- *              written min = -0.0 / max = +0.0. */
+ *              written min = -0.0 / max = +0.0.
+ *
+ * first / last (HX_AGG_FIRST, HX_AGG_LAST): a group is series_id, or
+ * (series_id, floor(ts / bucket_ms)). `last` is the value of the group's
+ * surviving non-null row with the greatest timestamp and `last_ts` that
+ * timestamp; `first` / `first_ts` the same with the smallest. "Surviving" is
+ * what every other aggregate means: after the ts-range filter, the series-set
+ * filter and dedup. A null is still a row for dedup (a newer null shadows an
+ * older value) and drops out afterwards, so `last` is the latest NON-NULL
+ * survivor; a group without one is not emitted, as for the other ops.
+ *   value      the 64 bits of the chosen value come back unchanged: NaN
+ *              payload, signalling bit, the sign of zero, subnormals. The
+ *              stale marker 0x7FF0000000000002 is a value: if it is a series'
+ *              latest sample, `last` returns exactly it.
+ *   timestamp  full-range int64: negative timestamps and an unbounded query
+ *              range work.
+ *   ties       after dedup two survivors of one group share a timestamp only
+ *              if the same primary key survives in two time segments
+ *              (segments are unioned without dedup). Among the rows tied at
+ *              the extreme timestamp the value greatest in totalOrder wins,
+ *              for first and for last: arbitrary, but deterministic and
+ *              independent of row position, as min/max are.
+ *   devices    on more than one device the partials merge by the same rules
+ *              (greater last_ts, smaller first_ts, ties to the totalOrder-
+ *              greater value), on bit patterns: no exception as for
+ *              vmin/vmax above.
+ * A request of only FIRST and/or LAST is valid. On a Binary value store they
+ * are refused like every aggregate (HX_ERR_UNSUPPORTED). */
 typedef struct {
     uint32_t ops;         /* OR of HX_AGG_*  (over the value column) */
     int64_t  bucket_ms;   /* 0: group by series_id; >0: by (series_id,
@@ -163,6 +192,16 @@ typedef struct hx_result_table {
     const double*   vmin;
     const double*   vmax;
     const double*   avg;
+    /* Appended members. Tables are produced by the library and handed out
+     * by pointer, so callers built against the eight-member struct keep
+     * working (hx_col_batch.validity is the precedent). first / first_ts
+     * are non-NULL iff HX_AGG_FIRST was asked, last / last_ts iff
+     * HX_AGG_LAST. The values are f64 bit patterns: read them as 64-bit
+     * words where a NaN payload matters. */
+    const double*   first;
+    const int64_t*  first_ts;
+    const double*   last;
+    const int64_t*  last_ts;
 } hx_result_table;
 
 /* Streaming columnar batch for the non-aggregating parity mode — the
